@@ -22,9 +22,16 @@ timed K steps then measure the steady state a continuously running receiver sees
 Multi-GPU: one process per GPU (torch.distributed.run); every rank processes its
 own independent stream shard (weak scaling, no data-path collective).
 
-Also reports: the dominant kernel's roofline (algorithmic bytes / average launch
-time from HIP events recorded on the launch stream) and a CPU baseline (the
-oracle restatement, timed on this host on a bounded sample, rank 0 at N=1 only).
+A plain run does only that: set up, warm up, time the K steps, print the line.
+--dump-outputs DIR then writes what the last timed step computed (acquisition
+results, tracking records) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+--full also reports: the dominant kernel's roofline (algorithmic bytes / average
+launch time from HIP events recorded on the launch stream), a sanity check of the
+timed region's outputs, the acquisition-only and tracking-only rates and a CPU
+baseline (the oracle restatement, timed on this host on a bounded sample, rank 0 at
+N=1 only).
 """
 import argparse
 import json
@@ -509,15 +516,28 @@ def run_c5(args):
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if shared_device_rehearsal() else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    # sanity on the timed region's outputs: acquisitions of the visible satellites,
+    names = ("gps", "gal", "bds")
+    if args.dump_outputs:
+        # the last timed step: each signal's acquisition results, and each pool's general_work
+        # records over that step's span (the timed launch's calls [(K - 1) * per_step,
+        # K * per_step) per channel; with --trk-replay the last step's own launch)
+        for name, a, b0, nb, stride, res, P5, N5 in acqs:
+            dump_records(args.dump_outputs, "acq_" + name,
+                         res.cpu().numpy().view(gsdr.ACQ_RESULT_DTYPE).reshape(nb, P5), rank)
+        for pl in pools:
+            ep = K * pl["per_step"] if stream else pl["epochs"]  # the timed launch's max_epochs (record layout)
+            last = pl["per_step"] if stream else pl["epochs"]
+            recs = pl["out"].cpu().numpy().view(gsdr.TRK_EPOCH_DTYPE)[:pl["nch"] * ep].reshape(pl["nch"], ep)
+            dump_records(args.dump_outputs, "trk_" + names[pl["sig"]],
+                         last_step_records(recs, pl["cnt"].cpu().numpy(), ep - last, last), rank)
+    # sanity (--full) on the timed region's outputs: acquisitions of the visible satellites,
     # tracking records per channel, carrier Doppler of the last 16 calls vs the truth
     det = {}
-    for name, a, b0, nb, stride, res, P5, N5 in acqs:
+    for name, a, b0, nb, stride, res, P5, N5 in acqs if args.full else ():
         r = res.cpu().numpy().view(gsdr.ACQ_RESULT_DTYPE).reshape(nb, P5)
         det[name] = sorted({int(x["prn"]) for x in r[0] if x["positive"]})
-    names = ("gps", "gal", "bds")
     calls, conv = {}, {}
-    for pl in pools:
+    for pl in pools if args.full else ():
         cnt = pl["cnt"].cpu().numpy()
         calls[names[pl["sig"]]] = int(cnt.min())
         recs = pl["out"].cpu().numpy().view(gsdr.TRK_EPOCH_DTYPE).reshape(pl["nch"], pl["epochs"])
@@ -531,6 +551,55 @@ def run_c5(args):
         flops += nb * (Dn * (5 * N5 * math.log2(N5) + 6 * N5) + P5 * Dn * (5 * N5 * math.log2(N5) + 11 * N5))
     samples = world * K * B * n
     value = samples / elapsed / 1e6
+
+    head = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": round(elapsed / K * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded 25 Msps IQ: 12 GPS L1 C/A + 12 Galileo E1 + 8 BeiDou B1I at 45 dB-Hz + AWGN; "
+                "one stream per job)",
+        "config": {
+            "workload": "C5: hybrid GPS L1 C/A + Galileo E1 + BeiDou B1I, 25 Msps, %d channels sharded c %% world "
+                        "(12/12/8 per 32-channel share); per 4 ms of the rank's span 2 GPS + 2 BeiDou 32 PRN x 80 "
+                        "Doppler grids (N 25000) and 1 Galileo 36 PRN x 40 Doppler grid (N 100000)" % C5_CHANNELS,
+            "blocks_per_step": total, "blocks_per_rank": B, "fs_sps": fs,
+            "parallelism": "one stream of %d ms per step: acquisition blocks [%d,%d) and %d channels (GPS %d, "
+                           "Galileo %d, BeiDou %d) on rank %d of %d, no data-path collective"
+                           % (total, lo, hi, len(plan["channels"]), len(plan["pools"][0]), len(plan["pools"][1]),
+                              len(plan["pools"][2]), rank, world),
+            "tracking": ("one continuous stream (periodic %d ms span repeated end to end), one launch per pool per "
+                         "timed region" % total if stream else
+                         "each step re-tracks the span from the channels' saved start states (one launch per pool)")},
+        "real_time_factor": round(value * 1e6 / fs, 2),
+        "prewarm": {"min_ms": args.min_warmup_ms, "acq_passes": prewarm_passes,
+                    "note": "untimed acquisition passes before the W warmup steps (GPU clock ramp)"},
+    }
+
+    def finish(line):
+        if shared_device_rehearsal() and world > 1:
+            line["rehearsal"] = ("%d ranks sharing %d device(s) over gloo (GSDR_BENCH_SHARED_DEVICE): the multi-rank "
+                                 "path on real engines, not a scaling number" % (world, torch.cuda.device_count()))
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        for pl in pools:
+            pl["t"].close()
+        for _, a, *_ in acqs:
+            a.close()
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        # the headline alone; the stages' own runs, the per-rank and H2D figures and the
+        # check of the outputs follow only with --full
+        return finish(head)
 
     def timed_part(fn):
         torch.cuda.synchronize(dev)
@@ -583,32 +652,7 @@ def run_c5(args):
     else:
         gathered = [mine]
     line = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": round(elapsed / K * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded 25 Msps IQ: 12 GPS L1 C/A + 12 Galileo E1 + 8 BeiDou B1I at 45 dB-Hz + AWGN; "
-                "one stream per job)",
-        "config": {
-            "workload": "C5: hybrid GPS L1 C/A + Galileo E1 + BeiDou B1I, 25 Msps, %d channels sharded c %% world "
-                        "(12/12/8 per 32-channel share); per 4 ms of the rank's span 2 GPS + 2 BeiDou 32 PRN x 80 "
-                        "Doppler grids (N 25000) and 1 Galileo 36 PRN x 40 Doppler grid (N 100000)" % C5_CHANNELS,
-            "blocks_per_step": total, "blocks_per_rank": B, "fs_sps": fs,
-            "parallelism": "one stream of %d ms per step: acquisition blocks [%d,%d) and %d channels (GPS %d, "
-                           "Galileo %d, BeiDou %d) on rank %d of %d, no data-path collective"
-                           % (total, lo, hi, len(plan["channels"]), len(plan["pools"][0]), len(plan["pools"][1]),
-                              len(plan["pools"][2]), rank, world),
-            "tracking": ("one continuous stream (periodic %d ms span repeated end to end), one launch per pool per "
-                         "timed region" % total if stream else
-                         "each step re-tracks the span from the channels' saved start states (one launch per pool)")},
-        "real_time_factor": round(value * 1e6 / fs, 2),
+        **head,
         "roofline": {"bound": "valu", "achieved": round(flops * K / elapsed / 1e12, 2), "peak": FP32_PEAK / 1e12,
                      "unit": "TFLOP/s", "frac": round(flops * K / elapsed / FP32_PEAK, 4), "traffic": None,
                      "note": "nominal FFT flops of the rank's acquisition grids over the whole step (tracking and "
@@ -632,20 +676,8 @@ def run_c5(args):
                             "convergence is not comparable with full-Doppler runs" if stream else
                             "replay mode: the same span every step, full +-4 kHz Dopplers")},
         "cpu_baseline": None,
-        "prewarm": {"min_ms": args.min_warmup_ms, "acq_passes": prewarm_passes,
-                    "note": "untimed acquisition passes before the W warmup steps (GPU clock ramp)"},
     }
-    if shared_device_rehearsal() and world > 1:
-        line["rehearsal"] = ("%d ranks sharing %d device(s) over gloo (GSDR_BENCH_SHARED_DEVICE): the multi-rank "
-                             "path on real engines, not a scaling number" % (world, torch.cuda.device_count()))
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    for pl in pools:
-        pl["t"].close()
-    for _, a, *_ in acqs:
-        a.close()
-    if dist is not None:
-        dist.destroy_process_group()
+    finish(line)
 
 
 def clock_warmup(acq_pass, ms, sync):
@@ -671,6 +703,27 @@ def clock_warmup(acq_pass, ms, sync):
         acq_pass(n)
         n += 1
     return n
+
+
+def last_step_records(recs, counts, first, n):
+    """Calls first .. first + n of every channel from the record array [channels, epochs] of
+    a tracking launch; a call the channel did not make (index >= its count) is all zeros,
+    whatever an earlier launch left in the buffer."""
+    out = recs[:, first:first + n].copy()
+    made = np.arange(first, first + out.shape[1])[None, :] < np.asarray(counts, np.int64)[:, None]
+    out[~made] = np.zeros((), recs.dtype)
+    return out
+
+
+def dump_records(dirname, prefix, recs, rank=0):
+    """--dump-outputs: every field of a structured record array as
+    DIR/<prefix>_<field>.npy in float64 (the integer fields are exact in it), with the
+    array's own shape; ranks other than 0 add .rank<r> before the extension."""
+    os.makedirs(dirname, exist_ok=True)
+    tail = ".npy" if rank == 0 else ".rank%d.npy" % rank
+    for f in recs.dtype.names:
+        if f != "reserved":
+            np.save(os.path.join(dirname, "%s_%s%s" % (prefix, f, tail)), np.ascontiguousarray(recs[f]).astype(np.float64))
 
 
 # GSDR_BENCH_SHARED_DEVICE=1: a multi-rank rehearsal on a box with fewer GPUs than ranks --
@@ -724,8 +777,17 @@ def main(argv=None, backend=DeviceBackend):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--blocks", type=int, default=64, help="1 ms blocks per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile-events", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check the rest: the stages' HIP-event profile and the "
+                         "dominant kernel's roofline, the sanity check of the timed region's outputs, the "
+                         "acquisition-only / tracking-only rates, the CPU baseline (c5: the components, per-rank and "
+                         "H2D figures and the check).  Without it the run sets up, warms up, times the steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (its acquisition results and "
+                         "its tracking records) as DIR/<name>.npy, float64; same arguments, same inputs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile-events", action="store_true", help="with --full: no HIP-event profile / roofline")
     ap.add_argument("--cu-partition", action="store_true",
                     help="give the tracking stream CHANNELS CUs of its own and acquisition the rest")
     ap.add_argument("--trk-cus", type=int, default=0,
@@ -760,6 +822,7 @@ def main(argv=None, backend=DeviceBackend):
                          "job, 256 channels sharded c %% world, acquisition block spans per rank")
     args = ap.parse_args(argv)
     args.trk_stream = not args.trk_replay
+    profile = args.full and not args.no_profile_events
     if args.workload == "c5":
         return run_c5(args)
 
@@ -875,7 +938,7 @@ def main(argv=None, backend=DeviceBackend):
     # The sanity check below reads the timed region's own outputs after it ends, so
     # the GPU goes from the warmup steps straight into the timed steps instead of
     # idling while the host inspects results (an idle gap lets the clocks drop).
-    if not args.no_profile_events:
+    if profile:
         for a in acqs:
             a.set_profiling(True)
             a.read_profile()
@@ -886,7 +949,7 @@ def main(argv=None, backend=DeviceBackend):
         dist.barrier()
     be.synchronize()
     # common time base for the chains' stage intervals (their busy-time union)
-    ref_ev = None if args.no_profile_events else be.event()
+    ref_ev = be.event() if profile else None
     if ref_ev is not None:
         ref_ev.record()
     t0 = time.perf_counter()
@@ -903,18 +966,31 @@ def main(argv=None, backend=DeviceBackend):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    trk_calls_timed = int(trk_n.cpu().numpy().min()) if do_trk else 0
-    # sanity, on the timed region's outputs: the visible satellites are acquired
+    # the timed region's own outputs, read back before anything else runs on the handles
+    res, recs, nrec = None, None, np.zeros(1, np.int64)
+    ep_chk = K * total if args.trk_stream else total  # the timed launch's max_epochs (record layout)
+    if args.full or args.dump_outputs:
+        res = res_dev.cpu().numpy().view(gsdr.ACQ_RESULT_DTYPE).reshape(B, P)
+        if do_trk:
+            recs = trk_out.cpu().numpy().view(gsdr.TRK_EPOCH_DTYPE)[:nloc * ep_chk].reshape(nloc, ep_chk)
+            nrec = trk_n.cpu().numpy()
+    if args.dump_outputs:
+        # the last timed step: its B x P acquisition results, and each channel's general_work
+        # records over that step's span of the stream (calls [(K - 1) * total, K * total) of
+        # the timed launch; with --trk-replay the last step's own launch)
+        if args.only != "trk":
+            dump_records(args.dump_outputs, "acq", res, rank)
+        if do_trk:
+            dump_records(args.dump_outputs, "trk", last_step_records(recs, nrec, ep_chk - total, total), rank)
+    trk_calls_timed = int(nrec.min()) if do_trk else 0
+    # sanity (--full), on the timed region's outputs: the visible satellites are acquired
     # (every step acquires the same blocks) and tracked with a strong prompt (the
     # continuous stream's last calls; with --trk-replay the last step's 64 ms)
-    res = res_dev.cpu().numpy().view(gsdr.ACQ_RESULT_DTYPE).reshape(B, P)
-    det = {int(r["prn"]) for r in res[0] if r["positive"]}
     vis = {s.prn for s in sats}
-    prompt_ratio, dop_err, nrec = None, None, np.zeros(1, np.int64)
-    if do_trk:
-        ep_chk = K * total if args.trk_stream else total  # the timed launch's max_epochs (record layout)
-        recs = trk_out.cpu().numpy().view(gsdr.TRK_EPOCH_DTYPE)[:nloc * ep_chk].reshape(nloc, ep_chk)
-        nrec = trk_n.cpu().numpy()
+    det, prompt_ratio, dop_err = set(), None, None
+    if args.full:
+        det = {int(r["prn"]) for r in res[0] if r["positive"]}
+    if args.full and do_trk:
         taps = np.stack([recs[i][nrec[i] - 1]["taps"][:6].view(np.complex64) for i in range(nloc)])
         prompt_ratio = float(np.median(np.abs(taps[:, 1]) / np.maximum(np.abs(taps[:, 0]), 1e-9)))
         # carrier Doppler averaged over the last 16 calls (one call's value carries
@@ -925,7 +1001,7 @@ def main(argv=None, backend=DeviceBackend):
     stage_ms, stage_n, stage_busy = (np.zeros(4), np.zeros(4, np.uint32), np.zeros(4))
     trk_ms, trk_launches = 0.0, 0
     corr_union_ms = None
-    if not args.no_profile_events:
+    if profile:
         # the correlate stage's busy time over all chains: the union of every
         # launch interval of every handle against one reference event
         iv = []
@@ -995,7 +1071,7 @@ def main(argv=None, backend=DeviceBackend):
     }
     if args.only:
         line["diagnostic_only_stage"] = args.only
-    if not args.no_profile_events and stage_n[1] > 0:
+    if profile and stage_n[1] > 0:
         # a step holds stage_n / steps correlate launches (one per chain), each over
         # B * steps / stage_n blocks.  The chains' launches run concurrently on
         # their streams and share the chip, so a launch's duration counts the time
@@ -1065,19 +1141,21 @@ def main(argv=None, backend=DeviceBackend):
             "acq_launches_per_step": round(stage_n[1] / args.steps, 2),
         }
     line["acq_roof_frac_whole_step"] = round(acq_bytes_per_block() * B / (ms_per_step / 1e3) / HBM_PEAK, 4)
-    line["check"] = {"visible": len(vis), "acquired_block0": len(vis & det),
-                     "median_prompt_over_early": None if prompt_ratio is None else round(prompt_ratio, 2),
-                     "prompt_over_early_theory": round(1.0 / (1.0 - 0.25), 2),
-                     "trk_calls_per_channel": int(nrec.min()),
-                     "trk_calls_per_channel_timed": trk_calls_timed,
-                     "median_mean16_doppler_err_hz": None if dop_err is None else round(float(np.median(dop_err)), 2),
-                     "channels_within_25hz": None if dop_err is None else int(np.sum(dop_err < 25.0))}
+    if args.full:
+        line["check"] = {"visible": len(vis), "acquired_block0": len(vis & det),
+                         "median_prompt_over_early": None if prompt_ratio is None else round(prompt_ratio, 2),
+                         "prompt_over_early_theory": round(1.0 / (1.0 - 0.25), 2),
+                         "trk_calls_per_channel": int(nrec.min()),
+                         "trk_calls_per_channel_timed": trk_calls_timed,
+                         "median_mean16_doppler_err_hz": (None if dop_err is None
+                                                          else round(float(np.median(dop_err)), 2)),
+                         "channels_within_25hz": None if dop_err is None else int(np.sum(dop_err < 25.0))}
     # Acquisition-only and tracking-only rates, each timed over K steps
     # after the headline's timed region with the same handles: the acquisition
     # chains without the tracking launch, and the tracking launch alone (restarted
     # from the saved start state, K steps of the continuous stream).
-    if args.only is None and do_trk and args.trk_stream:
-        if not args.no_profile_events:
+    if args.full and args.only is None and do_trk and args.trk_stream:
+        if profile:
             for a in acqs:
                 a.set_profiling(False)
             trk.set_profiling(False)
@@ -1113,7 +1191,7 @@ def main(argv=None, backend=DeviceBackend):
             "trk_only_channels": nloc,
             "note": "each over K steps after the timed region; trk_only = the stream's IQ rate through the tracking "
                     "pool (every channel processes every sample)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(iq, codes, sats)
     if shared_device_rehearsal() and world > 1:
         line["rehearsal"] = ("%d ranks sharing %d device(s) over gloo (GSDR_BENCH_SHARED_DEVICE): the multi-rank "

@@ -3,7 +3,7 @@
 # one command (bench.py or profiles/configs_bench.py) under each environment
 # setting given, each run under its own time limit, the chain stopping at the
 # first failure.  Results: gpurun_out/$TAG/ab_<i>.json (+ .err), summary lines.
-#   gpurun -- bash profiles/ab_sweep.sh TAG "python bench.py --steps 20 --warmup 5" \
+#   bash profiles/ab_sweep.sh TAG "python bench.py --full --no-cpu-baseline --steps 20 --warmup 5" \
 #       "GSDR_ACQ_SPLIT=0" "GSDR_ACQ_SPLIT=1"
 #   gpurun -- bash profiles/ab_sweep.sh TAG "python profiles/configs_bench.py --only C5" "GSDR_ACQ_CORR_VARIANT=93"
 set -o pipefail

@@ -18,7 +18,7 @@ grep -E "tracking blocks|channel fsm" "$OUT/pytest_gpu.log" | head -3;
 echo "== smoke" &&
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 && cat "$OUT/smoke.log" &&
 echo "== bench" &&
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json" &&
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json" &&
 echo "== rocprof" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
     python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > "$OUT/bench_prof.json" 2> "$OUT/prof.err" &&
@@ -27,7 +27,7 @@ echo "== torchrun (world size 1, RCCL init + barrier + max-reduce path of bench.
 timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
     --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 5 --no-cpu-baseline > "$OUT/bench_torchrun.json" 2> "$OUT/bench_torchrun.err" &&
 echo "== c5" &&
-timeout -k 10 300 python bench.py --workload c5 --steps 20 --warmup 5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &&
+timeout -k 10 300 python bench.py --workload c5 --full --steps 20 --warmup 5 > "$OUT/bench_c5.json" 2> "$OUT/bench_c5.err" &&
 echo "== configs" &&
 timeout -k 10 300 python -u profiles/configs_bench.py --reps 5 > "$OUT/configs.jsonl" 2> "$OUT/configs.err" &&
 echo "== receiver (the drop-in path: factory-built pooled tracking blocks + acquisition services, 2 s)" &&

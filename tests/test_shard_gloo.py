@@ -309,7 +309,7 @@ def _bench_worker(rank, world, port, q):
     out = io.StringIO()
     try:
         with contextlib.redirect_stdout(out):
-            bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--no-profile-events",
+            bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--no-profile-events",
                         "--no-cpu-baseline", "--min-warmup-ms", "0"], backend=CpuBackend)
     except BaseException as e:  # report instead of leaving the parent waiting
         q.put((rank, None, repr(e)))
@@ -393,8 +393,8 @@ def test_bench_acq_stagger_tiles_each_step(monkeypatch):
 
     out = io.StringIO()
     with contextlib.redirect_stdout(out):
-        bench.main(["--steps", "3", "--warmup", "1", "--no-profile-events", "--no-cpu-baseline", "--acq-stagger", "8",
-                    "--min-warmup-ms", "0"], backend=CpuBackend)
+        bench.main(["--steps", "3", "--warmup", "1", "--full", "--no-profile-events", "--no-cpu-baseline",
+                    "--acq-stagger", "8", "--min-warmup-ms", "0"], backend=CpuBackend)
     line = json.loads(out.getvalue().strip().splitlines()[-1])
     B = line["config"]["blocks_per_step"]
     assert line["config"]["acq_stagger"] == 8
@@ -407,6 +407,65 @@ def test_bench_acq_stagger_tiles_each_step(monkeypatch):
         assert (a[2], b[2]) == (first, B - first)
         span = (s if s < 4 else s - 4) * B
         assert a[1] - span == 0 and b[1] - span == a[2]
+
+
+def test_bench_plain_run_times_only_the_steps_and_dumps_the_last_one(monkeypatch, tmp_path):
+    """Without --full the C2 path launches the warmup and the timed steps and nothing else
+    (no acquisition-only / tracking-only passes, no check, no CPU baseline), and
+    --dump-outputs writes the last step's results: one float64 array per record field."""
+    import contextlib
+    import io
+    import json
+    import bench
+    import gsdr
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    log = []
+
+    class CpuBackend:
+        dist_backend = "gloo"
+
+        def __init__(self, local):
+            self.torch, self.dev = torch, torch.device("cpu")
+            self.gsdr = _StubEngine(log, 0)
+
+        def dist_kwargs(self):
+            return {}
+
+        def synchronize(self):
+            pass
+
+        def event(self):
+            raise AssertionError("no profile events in a plain run")
+
+    out = io.StringIO()
+    with contextlib.redirect_stdout(out):
+        bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--min-warmup-ms", "0", "--dump-outputs",
+                    str(tmp_path / "dump")], backend=CpuBackend)
+    line = json.loads(out.getvalue().strip().splitlines()[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line
+    assert line["steps"] == 3 and line["unit"] == "Msamples/s" and line["dtype"] == "f32"
+    for key in ("check", "components", "cpu_baseline", "roofline", "stages_us_per_launch"):
+        assert key not in line
+    B = line["config"]["blocks_per_step"]
+    assert len([e for e in log if e[0] == "acq"]) == 2 * 4  # (1 warmup + 3 timed) steps x two chains
+    assert [e for e in log if e[0] == "trk"] == [("trk", 1 * B), ("trk", 3 * B)]
+    for f in gsdr.ACQ_RESULT_DTYPE.names:
+        a = np.load(tmp_path / "dump" / ("acq_%s.npy" % f))
+        assert a.dtype == np.float64 and a.shape == (B, bench.P)
+    t = np.load(tmp_path / "dump" / "trk_taps.npy")
+    assert t.dtype == np.float64 and t.shape == (bench.CHANNELS, B, 10)
+
+
+def test_bench_last_step_records_blank_the_calls_not_made():
+    import bench
+    import gsdr
+    recs = np.zeros((2, 6), gsdr.TRK_EPOCH_DTYPE)
+    recs["consumed"] = np.arange(12).reshape(2, 6) + 1
+    last = bench.last_step_records(recs, [6, 5], 4, 2)
+    assert last["consumed"].tolist() == [[5, 6], [11, 0]]  # channel 1 made 5 calls: its call 5 is blank
+    assert recs["consumed"][1, 5] == 12  # a copy: the launch's own records are untouched
 
 
 def test_bench_clock_warmup_precedes_the_warmup_steps():
