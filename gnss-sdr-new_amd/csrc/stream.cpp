@@ -56,6 +56,9 @@ struct gsdr_stream
     };
     std::vector<Pending> pending;
     uint64_t landed{0};  // every item before it is in device memory
+    // filled by a device-side producer (StreamWriter, decim.hip) on `copy`: no host
+    // memory is held, so `landed` follows `head`, and gsdr_stream_push is refused
+    bool device_produced{false};
     std::vector<hipEvent_t> retired;  // waited for by a push, recycled once complete
     std::vector<hipEvent_t> spare;
     // windows handed out by gsdr_stream_window_async whose reads are not yet
@@ -76,6 +79,9 @@ namespace gsdr
 {
 int stream_item_type(const gsdr_stream* s) { return s->item_type; }
 int stream_device(const gsdr_stream* s) { return s->device; }
+uint64_t stream_capacity(const gsdr_stream* s) { return s->cap; }
+uint64_t stream_window(const gsdr_stream* s) { return s->window; }
+void stream_set_device_produced(gsdr_stream* s) { s->device_produced = true; }
 
 namespace
 {
@@ -186,6 +192,63 @@ int StreamReader::acquire(hipStream_t consumer)
     return GSDR_OK;
 }
 int StreamReader::release(hipStream_t consumer) { return release_locked(s_, consumer, lo_ == UINT64_MAX ? 0 : lo_); }
+bool StreamReader::bounds(uint64_t* base, uint64_t* oldest, uint64_t* head) const
+{
+    *base = s_->base;
+    *oldest = oldest_of(s_);
+    *head = s_->head;
+    return s_->started;
+}
+
+StreamWriter::StreamWriter(gsdr_stream* s) : s_(s), lk_(s->mu) {}
+hipStream_t StreamWriter::stream() const { return s_->copy; }
+uint64_t StreamWriter::head() const { return s_->head; }
+int StreamWriter::reserve(uint64_t first, uint64_t n, void** ring, uint64_t* cap, uint64_t* window)
+{
+    GSDR_REQUIRE(s_->device_produced, GSDR_E_STATE, "gsdr_stream: not a device-produced ring");
+    GSDR_REQUIRE(n <= s_->cap, GSDR_E_ARG, "gsdr_stream: %llu produced items exceed the ring capacity %llu",
+        (unsigned long long)n, (unsigned long long)s_->cap);
+    if (!s_->started)
+        {
+            s_->started = true;
+            s_->base = s_->head = s_->landed = first;
+        }
+    GSDR_REQUIRE(first == s_->head, GSDR_E_ARG, "gsdr_stream: produced items must be contiguous (next is %llu, got %llu)",
+        (unsigned long long)s_->head, (unsigned long long)first);
+    // the rule of a push: what it overwrites must have been read.  An async window
+    // still open over those items has no reader event yet; the producer does not
+    // block on it (it is called under the decimator's lock), it fails instead.
+    const uint64_t overwritten = s_->head + n > s_->cap ? s_->head + n - s_->cap : 0;
+    for (const auto& w : s_->open)
+        GSDR_REQUIRE(w.first >= overwritten, GSDR_E_STATE,
+            "gsdr_stream: the producer would overwrite the window at %llu still open (gsdr_stream_release missing)",
+            (unsigned long long)w.first);
+    for (auto it = s_->readers.begin(); it != s_->readers.end();)
+        {
+            if (it->lo < overwritten)
+                {
+                    GSDR_HIP(hipStreamWaitEvent(s_->copy, it->ev, 0));
+                    s_->retired.push_back(it->ev);
+                    it = s_->readers.erase(it);
+                }
+            else
+                ++it;
+        }
+    if (s_->readers.size() + s_->retired.size() >= 16) recycle_locked(s_);
+    *ring = s_->d_ring;
+    *cap = s_->cap;
+    *window = s_->window;
+    reserved_ = n;
+    return GSDR_OK;
+}
+int StreamWriter::commit()
+{
+    GSDR_HIP(hipEventRecord(s_->pushed, s_->copy));
+    s_->head += reserved_;
+    s_->landed = s_->head;
+    reserved_ = 0;
+    return GSDR_OK;
+}
 }  // namespace gsdr
 
 namespace
@@ -254,6 +317,8 @@ int gsdr_stream_push(gsdr_stream* s, const void* iq_host, uint64_t first_sample,
 {
     GSDR_REQUIRE(s && (iq_host || n == 0), GSDR_E_ARG, "gsdr_stream_push: null argument");
     std::unique_lock<std::mutex> lk(s->mu);
+    GSDR_REQUIRE(!s->device_produced, GSDR_E_STATE,
+        "gsdr_stream_push: the ring is a decimator's output (filled on the device by gsdr_decim_advance)");
     gsdr::DeviceGuard g(s->device);
     if (!s->started)
         {
@@ -415,6 +480,32 @@ int gsdr_stream_release(gsdr_stream* s, void* consumer_stream)
     }), s->open.end());
     s->released.notify_all();
     return rc;
+}
+
+int gsdr_stream_read(gsdr_stream* s, uint64_t first, uint64_t n, void* host_out)
+{
+    GSDR_REQUIRE(s && (host_out || n == 0), GSDR_E_ARG, "gsdr_stream_read: null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    GSDR_REQUIRE(s->started, GSDR_E_STATE, "gsdr_stream_read: nothing pushed yet");
+    const uint64_t oldest = gsdr::oldest_of(s);
+    GSDR_REQUIRE(first >= oldest && first + n <= s->head, GSDR_E_ARG,
+        "gsdr_stream_read: items [%llu, %llu) outside the ring's [%llu, %llu)", (unsigned long long)first,
+        (unsigned long long)(first + n), (unsigned long long)oldest, (unsigned long long)s->head);
+    if (n == 0) return GSDR_OK;
+    gsdr::DeviceGuard g(s->device);
+    GSDR_HIP(hipEventSynchronize(s->pushed));
+    // the ring lock is held: no push or producer overwrites the items meanwhile
+    auto* dst = static_cast<uint8_t*>(host_out);
+    uint64_t done = 0;
+    while (done < n)
+        {
+            const uint64_t pos = (first + done) % s->cap;
+            const uint64_t len = std::min<uint64_t>(n - done, s->cap - pos);
+            GSDR_HIP(hipMemcpy(dst + done * s->item_bytes, s->d_ring + pos * s->item_bytes, len * s->item_bytes,
+                hipMemcpyDeviceToHost));
+            done += len;
+        }
+    return GSDR_OK;
 }
 
 int gsdr_stream_device(const gsdr_stream* s, int* device)

@@ -49,6 +49,8 @@ EXPORTED = [
     "gsdr_acq_set_active_prns", "gsdr_acq_submit_stream", "gsdr_acq_collect", "gsdr_host_register",
     "gsdr_host_unregister", "gsdr_trk_submit_stream", "gsdr_trk_collect", "gsdr_stream_landed",
     "gsdr_stream_wait_landed",
+    "gsdr_stream_read", "gsdr_firdes_low_pass", "gsdr_acq_resampler_plan", "gsdr_decim_create", "gsdr_decim_destroy",
+    "gsdr_decim_output", "gsdr_decim_advance",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -304,6 +306,14 @@ def load():
     L.gsdr_trk_run_stream_host.argtypes = [P, P, U32, P, P]
     L.gsdr_trk_submit_stream.argtypes = [P, P, U32]
     L.gsdr_trk_collect.argtypes = [P, ctypes.c_int, P, P, P]
+    L.gsdr_stream_read.argtypes = [P, U64, U64, P]
+    L.gsdr_firdes_low_pass.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, P, P]
+    L.gsdr_acq_resampler_plan.argtypes = [I64, ctypes.c_double, P, P, P]
+    L.gsdr_decim_create.argtypes = [P, U32, P, U32, U64, U64, P]
+    L.gsdr_decim_destroy.argtypes = [P]
+    L.gsdr_decim_destroy.restype = None
+    L.gsdr_decim_output.argtypes = [P, P]
+    L.gsdr_decim_advance.argtypes = [P, P]
     _lib = L
     return L
 
@@ -810,11 +820,94 @@ class Stream:
         finally:
             self.release(consumer_stream)
 
+    def read(self, first, n):
+        """Items [first, first + n) copied to the host (gsdr_stream_read, synchronous):
+        complex64 for a gr_complex ring, interleaved I,Q integers otherwise."""
+        n = int(n)
+        out = np.zeros(n if self.item_type == ITEM_GR_COMPLEX else 2 * n, _ITEM_NP[self.item_type])
+        _check(load().gsdr_stream_read(self._h, int(first), n, _ptr(out)))
+        return out
+
     @property
     def device(self):
         d = ctypes.c_int()
         _check(load().gsdr_stream_device(self._h, ctypes.byref(d)))
         return d.value
+
+
+class _BorrowedStream(Stream):
+    """A ring owned by another handle (a Decimator's output): never destroyed here."""
+
+    def __init__(self, handle, item_type, owner):
+        self._h = handle
+        self.item_type = int(item_type)
+        self._inflight = []
+        self._owner = owner  # keeps the owning handle alive while the wrapper is
+
+    def close(self):
+        self._h = ctypes.c_void_p()
+        self._owner = None
+
+
+def firdes_low_pass(gain, fs, cutoff, transition_width):
+    """firdes::low_pass (Hamming window) taps as float32 (gsdr_firdes_low_pass; host-only)."""
+    if not transition_width > 0 or not fs > 0:
+        raise GsdrError(GSDR_E_ARG, "firdes_low_pass: need fs > 0 and transition_width > 0")
+    cap = int(min(1e6, 53.0 * float(fs) / (22.0 * float(transition_width)))) + 2
+    taps = np.zeros(cap, np.float32)
+    n = ctypes.c_uint32(cap)
+    _check(load().gsdr_firdes_low_pass(float(gain), float(fs), float(cutoff), float(transition_width), _ptr(taps),
+                                       ctypes.byref(n)))
+    return taps[:n.value].copy()
+
+
+def acq_resampler_plan(fs_in, opt_fs):
+    """(decimation, ntaps, latency) of the acquisition resampler the reference builds
+    for input rate fs_in and optimum acquisition rate opt_fs (gsdr_acq_resampler_plan);
+    decimation 1 means none."""
+    d, t, lat = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().gsdr_acq_resampler_plan(int(fs_in), float(opt_fs), ctypes.byref(d), ctypes.byref(t),
+                                          ctypes.byref(lat)))
+    return d.value, t.value, lat.value
+
+
+class Decimator:
+    """Decimating FIR from a source Stream into a gr_complex ring of its own
+    (gsdr_decim_*): y[m] = sum_j taps[j] x[m*decimation - j] over absolute sample
+    indices.  `output` is a Stream every consumer reads; it belongs to the decimator."""
+
+    def __init__(self, source, decimation, taps, capacity_items, max_window_items):
+        taps = np.ascontiguousarray(taps, np.float32)
+        self._h = ctypes.c_void_p()
+        self._source = source  # the source ring must outlive the decimator
+        _check(load().gsdr_decim_create(source._h if source is not None else None, int(decimation), _ptr(taps),
+                                        len(taps), int(capacity_items), int(max_window_items), ctypes.byref(self._h)))
+        self.decimation = int(decimation)
+        self.ntaps = len(taps)
+        h = ctypes.c_void_p()
+        _check(load().gsdr_decim_output(self._h, ctypes.byref(h)))
+        self.output = _BorrowedStream(h, ITEM_GR_COMPLEX, self)
+
+    def advance(self):
+        """Filter every output that became ready (asynchronous); returns the output head."""
+        head = ctypes.c_uint64()
+        _check(load().gsdr_decim_advance(self._h, ctypes.byref(head)))
+        return head.value
+
+    def close(self):
+        if self._h:
+            out, self.output = self.output, None
+            if out is not None:
+                out.close()
+            load().gsdr_decim_destroy(self._h)
+            self._h = ctypes.c_void_p()
+        self._source = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def cu_partition(n_reserved, n_cus=256):

@@ -3,6 +3,7 @@
 #include "pcps_acquisition_mi355x.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -12,9 +13,19 @@ AcquisitionService::AcquisitionService(const Acq_Conf& conf, uint32_t max_reques
       d_max(max_requests),
       d_consumed(static_cast<uint32_t>(conf.sampled_ms * conf.samples_per_ms)),
       d_isz(conf.it_size),
-      d_batch(batch_blocks ? batch_blocks : 1)
+      d_batch(batch_blocks ? batch_blocks : 1),
+      d_device(device)
 {
     if (max_requests == 0) throw std::invalid_argument("AcquisitionService: max_requests must be > 0");
+    create_engine(pcps_acquisition_mi355x::engine_item_type(conf.item_type));
+    d_buffer.resize(static_cast<size_t>(d_consumed) * d_isz);
+    d_slots.resize(max_requests);
+    d_res.resize(static_cast<size_t>(d_batch) * max_requests);
+}
+
+void AcquisitionService::create_engine(int item_type)
+{
+    const Acq_Conf& conf = d_conf;
     gsdr_acq_conf c{};
     c.fs_in = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
     c.consumed_samples = d_consumed;
@@ -24,20 +35,40 @@ AcquisitionService::AcquisitionService(const Acq_Conf& conf, uint32_t max_reques
     c.doppler_step = static_cast<uint32_t>(conf.doppler_step);
     c.pfa = conf.use_CFAR_algorithm_flag ? conf.pfa : 0.0F;
     c.max_dwells = 1;
-    c.item_type = pcps_acquisition_mi355x::engine_item_type(conf.item_type);
-    c.max_prns = max_requests;
+    c.item_type = item_type;
+    c.max_prns = d_max;
     c.max_blocks = d_batch;
     c.sampled_ms = conf.sampled_ms;
     c.ms_per_code = conf.ms_per_code;
-    if (gsdr_acq_create(device, &c, &d_engine) != GSDR_OK)
+    if (gsdr_acq_create(d_device, &c, &d_engine) != GSDR_OK)
         throw std::runtime_error(std::string("AcquisitionService: ") + gsdr_last_error());
     // the configuration's carrier model, whatever GSDR_ACQ_WIPE says
     if (gsdr_acq_set_wipeoff(d_engine, conf.wipeoff_mode()) != GSDR_OK)
         throw std::runtime_error(std::string("AcquisitionService: ") + gsdr_last_error());
     gsdr_acq_get_threshold(d_engine, &d_threshold);
-    d_buffer.resize(static_cast<size_t>(d_consumed) * d_isz);
-    d_slots.resize(max_requests);
-    d_res.resize(static_cast<size_t>(d_batch) * max_requests);
+    d_engine_item = item_type;
+}
+
+void AcquisitionService::attach_resampler(std::shared_ptr<AcqResampler> resampler)
+{
+    if (!resampler) throw std::invalid_argument("AcquisitionService::attach_resampler: null resampler");
+    if (resampler->decimation() != static_cast<uint32_t>(d_conf.resampler_ratio) || !AcqResampler::wanted(d_conf))
+        throw std::invalid_argument("AcquisitionService::attach_resampler: the resampler's decimation is not the "
+                                    "configuration's resampler_ratio");
+    std::lock_guard<std::mutex> lk(d_mu);
+    // (requests not yet uploaded keep their replicas and survive the engine's re-creation)
+    bool uploaded = false;
+    for (const auto& x : d_slots) uploaded = uploaded || x.loaded;
+    if (uploaded || d_ring_started || d_sample_counter != 0)
+        throw std::logic_error("AcquisitionService::attach_resampler: attach before the first work call");
+    if (d_engine_item != GSDR_ITEM_GR_COMPLEX)
+        {
+            // the decimated ring holds gr_complex whatever the source's item type
+            gsdr_acq_destroy(d_engine);
+            d_engine = nullptr;
+            create_engine(GSDR_ITEM_GR_COMPLEX);
+        }
+    d_resampler = std::move(resampler);
 }
 
 AcquisitionService::~AcquisitionService()
@@ -155,7 +186,16 @@ void AcquisitionService::answer(const std::vector<gsdr_acq_result>& res, uint32_
                             }
                         else
                             {
-                                const gsdr_acq_result& r = res[static_cast<size_t>(b) * nprn + i];
+                                gsdr_acq_result r = res[static_cast<size_t>(b) * nprn + i];
+                                if (d_resampler)
+                                    {
+                                        // back to the input rate (pcps_acquisition.cc:699-705)
+                                        const auto ratio = static_cast<double>(d_conf.resampler_ratio);
+                                        r.acq_delay_samples =
+                                            r.acq_delay_samples * ratio - static_cast<double>(d_resampler->latency());
+                                        r.samplestamp = static_cast<uint64_t>(
+                                            std::rint(static_cast<double>(r.samplestamp) * ratio));
+                                    }
                                 ans.push_back({s.channel, s.done, r, r.test_statistic > d_threshold});
                             }
                     }
@@ -217,6 +257,16 @@ void AcquisitionService::flush()
 
 int AcquisitionService::work_ring(gsdr_stream* ring, uint64_t head)
 {
+    if (d_resampler)
+        {
+            // `ring` is the source; the batches run on its decimated image.  Output m is
+            // ready once source item m * d is in: every output below head / d is.
+            if (ring != d_resampler->source())
+                throw std::invalid_argument("AcquisitionService::work_ring: not the attached resampler's source ring");
+            (void)d_resampler->advance();
+            ring = d_resampler->output();
+            head /= d_resampler->decimation();
+        }
     if (!d_ring_started)
         {
             d_ring_started = true;

@@ -32,7 +32,10 @@
 #include <mutex>
 #include <vector>
 
+#include <memory>
+
 #include "acq_conf.h"
+#include "acq_resampler.h"
 #include "gsdr.h"
 
 class AcquisitionService
@@ -70,6 +73,20 @@ public:
     // answers the launches in flight (if any)
     void flush();
 
+    // GNSS-SDR.use_acquisition_resampler on the ring path: from now on work_ring,
+    // still called with the SOURCE ring and its head, advances the resampler and runs
+    // the batches in place on the decimated ring (gr_complex at conf.resampled_fs, the
+    // rate the requests' replicas are sampled at), blocks [cursor, head / decimation).
+    // The answers are mapped back to the input rate before the callbacks, as
+    // pcps_acquisition.cc:699-705 does: acq_delay_samples * ratio - latency,
+    // samplestamp = rint(stamp * ratio).  Before the first work / work_ring
+    // call (std::logic_error otherwise); the resampler's decimation must be
+    // the configuration's resampler_ratio (std::invalid_argument).  Unattached, the
+    // service reads the ring it is given.
+    void attach_resampler(std::shared_ptr<AcqResampler> resampler);
+    const std::shared_ptr<AcqResampler>& resampler() const { return d_resampler; }
+
+    const Acq_Conf& conf() const { return d_conf; }
     float threshold() const { return d_threshold; }
     uint64_t sample_counter() const { return d_sample_counter; }
     uint64_t grids_run() const { return d_grids; }          // blocks searched
@@ -95,6 +112,7 @@ private:
     };
     static constexpr size_t kMaxFlights = 2;  // gsdr_acq_submit_stream's queue depth
     void collect_oldest();
+    void create_engine(int item_type);
     // uploads the armed slots' pending replicas and sets the active PRN count;
     // false when nothing is armed (lock held)
     bool prepare_locked(std::vector<uint64_t>& gen);
@@ -108,7 +126,10 @@ private:
     uint32_t d_consumed;
     size_t d_isz;
     uint32_t d_batch;
+    int d_device;
+    int d_engine_item{GSDR_ITEM_GR_COMPLEX};
     gsdr_acq* d_engine{nullptr};
+    std::shared_ptr<AcqResampler> d_resampler;
     float d_threshold{0.0F};
     std::vector<Slot> d_slots;
     std::vector<uint8_t> d_buffer;

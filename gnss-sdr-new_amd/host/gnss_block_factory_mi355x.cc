@@ -47,4 +47,32 @@ std::unique_ptr<TrackingInterface> GetTrkBlock(const ConfigurationInterface* con
         return std::make_unique<BeidouB1iDllPllTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     return nullptr;
 }
+
+std::unique_ptr<AcquisitionService> GetAcqService(const ConfigurationInterface* configuration, const std::string& role,
+    const std::string& signal, uint32_t max_requests, gsdr_stream* ring, const std::string& ring_key,
+    uint32_t batch_blocks)
+{
+    // ms_per_code, chip rate and optimum acquisition rate of the signal's adapter
+    Acq_Conf conf;
+    double chip_rate, opt_freq;
+    if (signal == "1C")
+        conf.ms_per_code = 1, chip_rate = 1.023e6, opt_freq = 2000000.0;
+    else if (signal == "1B")
+        conf.ms_per_code = 4, chip_rate = 1.023e6, opt_freq = 2000000.0;
+    else if (signal == "B1")
+        conf.ms_per_code = 1, chip_rate = 2.046e6, opt_freq = 10e6;
+    else
+        return nullptr;
+    conf.SetFromConfiguration(configuration, role, chip_rate, opt_freq);
+    int device = 0;
+    if (!ring || gsdr_stream_device(ring, &device) != GSDR_OK) return nullptr;
+    auto svc = std::make_unique<AcquisitionService>(conf, max_requests, device, batch_blocks);
+    if (AcqResampler::wanted(conf))
+        {
+            // two launches of batch_blocks blocks in flight on the decimated ring
+            const uint64_t block = static_cast<uint64_t>(conf.sampled_ms * conf.samples_per_ms);
+            svc->attach_resampler(AcqResampler::get(ring, ring_key, signal, conf, 4 * batch_blocks * block));
+        }
+    return svc;
+}
 }  // namespace gsdr_factory

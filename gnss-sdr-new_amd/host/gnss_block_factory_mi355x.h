@@ -14,6 +14,7 @@
 #include <string>
 
 #include "acquisition_interface.h"
+#include "acquisition_service.h"
 #include "configuration.h"
 #include "tracking_interface.h"
 
@@ -31,6 +32,19 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
     unsigned int in_streams, unsigned int out_streams, int channel = 0);
 std::unique_ptr<TrackingInterface> GetTrkBlock(const ConfigurationInterface* configuration, const std::string& role,
     unsigned int in_streams, unsigned int out_streams, int channel = 0);
+
+// The batched acquisition service (acquisition_service.h) of `signal` -- "1C", "1B"
+// or "B1", with the constants of that signal's adapter -- for up to max_requests
+// channels reading the device ring `ring` (a DeviceIqRing's stream(); ring_key names
+// its input stream) on the ring's device.  With GNSS-SDR.use_acquisition_resampler set and a decimation
+// above 1 the service is attached to the process's resampler of (device, ring_key,
+// signal) (acq_resampler.h): every service of one signal and stream shares one
+// decimated ring, as the reference's channels share one FIR block
+// (gnss_flowgraph.cc:1069-1113), and the requests' replicas are sampled at
+// service->conf().resampled_fs.  nullptr for another signal.
+std::unique_ptr<AcquisitionService> GetAcqService(const ConfigurationInterface* configuration, const std::string& role,
+    const std::string& signal, uint32_t max_requests, gsdr_stream* ring, const std::string& ring_key = "rf0",
+    uint32_t batch_blocks = 4);
 }  // namespace gsdr_factory
 
 #endif

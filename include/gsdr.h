@@ -136,6 +136,66 @@ int gsdr_stream_window_async(gsdr_stream* stream, uint64_t first_sample, uint64_
 int gsdr_stream_release(gsdr_stream* stream, void* consumer_stream);
 /* The device the ring lives on (a consumer handle must be on the same device). */
 int gsdr_stream_device(const gsdr_stream* stream, int* device);
+/* Synchronous device-to-host copy of items [first, first + n) of any ring (after
+ * the pushes, or the decimator passes, so far): for tests and dumps.  GSDR_E_ARG
+ * if the ring does not hold them (any more). */
+int gsdr_stream_read(gsdr_stream* stream, uint64_t first, uint64_t n, void* host_out);
+
+/* ======================================================================== */
+/* Acquisition resampler — decimating low-pass FIR between two rings         */
+/* ======================================================================== */
+/*
+ * GNSS-SDR.use_acquisition_resampler: the reference inserts one
+ * gr::filter::fir_filter_ccf with firdes::low_pass taps per signal and RF channel
+ * in front of the acquisition blocks (gnss_flowgraph.cc:1012-1128), and PCPS runs
+ * at Acq_Conf::resampled_fs.  A gsdr_decim reads a source ring of any item type
+ * and fills a GSDR_ITEM_GR_COMPLEX ring of its own on the same device:
+ *
+ *   y[m] = sum_{j=0}^{T-1} taps[j] * x[m*d - j]
+ *
+ * over absolute source sample indices, x = 0 before the source's first pushed
+ * sample `base` (GNU Radio's zero history).  The first output is m0 =
+ * ceil(base / d); output m is ready once source item m*d has been pushed.  An
+ * output index times d is an input sample index (pcps_acquisition.cc:705).  fp32
+ * with one summation order per output (j ascending, fused multiply-add): the
+ * output bytes do not depend on how the input was split into pushes and calls.
+ */
+typedef struct gsdr_decim gsdr_decim;
+
+/* firdes::low_pass with the Hamming window.  Host-only.  *ntaps: capacity of taps
+ * in, tap count out (GSDR_E_ARG if the design does not fit).
+ *   ntaps = (int)(53 fs / (22 transition_width)), made odd by +1; M = (ntaps-1)/2;
+ *   w[n] = 0.54 - 0.46 cos(2 pi n / (ntaps-1)) as float; omega = 2 pi cutoff / fs;
+ *   taps[n+M] = (n == 0 ? omega/pi : sin(n omega)/(n pi)) w[n+M] as float,
+ *   scaled by gain / (taps[M] + 2 sum_{n=1..M} taps[n+M]).
+ * GSDR_E_ARG unless 0 < cutoff <= fs/2 and transition_width > 0. */
+int gsdr_firdes_low_pass(double gain, double fs, double cutoff, double transition_width, float* taps, uint32_t* ntaps);
+/* The resampler the reference builds for an acquisition at fs_in whose signal's
+ * optimum acquisition rate is opt_fs (acq_conf.cc:97-106,
+ * gnss_flowgraph.cc:1073-1087,1112): decimation = floor(fs_in / opt_fs) lowered to
+ * a divisor of fs_in; taps low_pass(1, fs_in, fs_d / 2.1, fs_d / 2) with fs_d =
+ * fs_in / decimation; latency = (ntaps - 1) / 2 input samples.  decimation 1 with
+ * ntaps = latency = 0: no resampler (fs_in <= opt_fs, or no divisor above 1). */
+int gsdr_acq_resampler_plan(int64_t fs_in, double opt_fs, uint32_t* decimation, uint32_t* ntaps, uint32_t* latency);
+/* 1 <= decimation <= 64 and 1 <= ntaps <= 1024 (GSDR_E_UNSUPPORTED beyond, GSDR_E_ARG
+ * for 0); the source ring's window must hold ntaps + decimation items.  The output
+ * ring (capacity_items, max_window_items as in gsdr_stream_create) belongs to the
+ * decimator: gsdr_decim_destroy destroys it, the caller never does, and
+ * gsdr_stream_push on it returns GSDR_E_STATE.  The source must outlive the
+ * decimator. */
+int gsdr_decim_create(gsdr_stream* source, uint32_t decimation, const float* taps, uint32_t ntaps, uint64_t capacity_items,
+    uint64_t max_window_items, gsdr_decim** out);
+void gsdr_decim_destroy(gsdr_decim* decim);
+/* The decimated ring: every consumer of a gsdr_stream reads it unchanged. */
+int gsdr_decim_output(gsdr_decim* decim, gsdr_stream** out);
+/* Filters every output that became ready since the last call; *out_head (may be
+ * NULL) is the output ring's head afterwards.  Asynchronous: the kernels wait for
+ * the source's pushes on the device and are recorded as a reader of the source;
+ * a backlog longer than the source's window takes several kernel passes.
+ * GSDR_E_STATE (reason in gsdr_last_error) when the source ring no longer holds
+ * the ntaps - 1 history items or the unfiltered backlog, or when a window of the
+ * output ring that a pass would overwrite is still open. */
+int gsdr_decim_advance(gsdr_decim* decim, uint64_t* out_head);
 
 /* ======================================================================== */
 /* Acquisition — PCPS (pcps_acquisition)                                     */
