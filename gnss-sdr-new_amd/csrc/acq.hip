@@ -340,6 +340,29 @@ int gsdr_acq_get_dims(const gsdr_acq* a, uint32_t* D, uint32_t* N)
     return GSDR_OK;
 }
 
+int gsdr_acq_get_plan(const gsdr_acq* a, int32_t* variant, int32_t* nthreads, int32_t* r1, int32_t* nstages,
+    int32_t radix[8])
+{
+    GSDR_REQUIRE(a, GSDR_E_ARG, "gsdr_acq_get_plan: null handle");
+    static_assert(gsdr::fft::kMaxStages == 8, "gsdr_acq_get_plan reports 8 radices");
+    const bool four = a->variant >= 20;
+    const Plan& p = four ? a->plan4.sub : a->plan;
+    if (variant) *variant = a->variant;
+    if (nthreads) *nthreads = a->nt;
+    if (r1) *r1 = four ? a->plan4.r1 : 0;
+    if (nstages) *nstages = p.nstages;
+    if (radix)
+        for (int i = 0; i < gsdr::fft::kMaxStages; ++i) radix[i] = i < p.nstages ? p.radix[i] : 1;
+    return GSDR_OK;
+}
+
+int gsdr_acq_get_split(const gsdr_acq* a, int32_t* split)
+{
+    GSDR_REQUIRE(a && split, GSDR_E_ARG, "gsdr_acq_get_split: null argument");
+    *split = a->split;
+    return GSDR_OK;
+}
+
 int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* prn, uint32_t nprn)
 {
     GSDR_REQUIRE(a && codes && prn, GSDR_E_ARG, "gsdr_acq_set_local_codes: null argument");

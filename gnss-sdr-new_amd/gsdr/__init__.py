@@ -50,7 +50,7 @@ EXPORTED = [
     "gsdr_host_unregister", "gsdr_trk_submit_stream", "gsdr_trk_collect", "gsdr_stream_landed",
     "gsdr_stream_wait_landed",
     "gsdr_stream_read", "gsdr_firdes_low_pass", "gsdr_acq_resampler_plan", "gsdr_decim_create", "gsdr_decim_destroy",
-    "gsdr_decim_output", "gsdr_decim_advance",
+    "gsdr_decim_output", "gsdr_decim_advance", "gsdr_acq_get_plan", "gsdr_acq_get_split",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -233,6 +233,8 @@ def load():
     L.gsdr_acq_destroy.argtypes = [P]
     L.gsdr_acq_destroy.restype = None
     L.gsdr_acq_get_dims.argtypes = [P, P, P]
+    L.gsdr_acq_get_plan.argtypes = [P, P, P, P, P, P]
+    L.gsdr_acq_get_split.argtypes = [P, P]
     L.gsdr_acq_set_local_codes.argtypes = [P, P, P, U32]
     L.gsdr_acq_set_doppler.argtypes = [P, ctypes.c_int32, U32, ctypes.c_int32]
     L.gsdr_acq_set_threshold.argtypes = [P, F]
@@ -390,6 +392,33 @@ class Acquisition:
         _check(load().gsdr_acq_set_local_codes(self._h, _ptr(codes), _ptr(prns), len(prns)))
         self.nprn = len(prns)
 
+    def set_local_code(self, slot, code, prn):
+        """set_local_code of one PRN slot (gsdr_acq_set_local_code): the other slots keep
+        their spectra; the active count grows to slot + 1 if needed."""
+        code = np.ascontiguousarray(code, np.complex64)
+        assert code.ndim == 1 and len(code) >= self.conf.consumed_samples
+        _check(load().gsdr_acq_set_local_code(self._h, int(slot), _ptr(code), int(prn)))
+        self.nprn = max(self.nprn, int(slot) + 1)
+
+    def set_active_prns(self, nprn):
+        """The grid launches search slots [0, nprn) (gsdr_acq_set_active_prns)."""
+        _check(load().gsdr_acq_set_active_prns(self._h, int(nprn)))
+        self.nprn = int(nprn)
+
+    @property
+    def plan(self):
+        """The FFT plan of the handle (gsdr_acq_get_plan / gsdr_acq_get_split): variant,
+        nthreads, r1 (0: an LDS size), radix (the LDS plan's stages, or the four-step's N2
+        sub-plan's; empty for the packed four-step's compile-time sub-plans) and split."""
+        v = np.zeros(4, np.int32)
+        radix = np.zeros(8, np.int32)
+        split = ctypes.c_int32()
+        L = load()
+        _check(L.gsdr_acq_get_plan(self._h, _ptr(v[0:]), _ptr(v[1:]), _ptr(v[2:]), _ptr(v[3:]), _ptr(radix)))
+        _check(L.gsdr_acq_get_split(self._h, ctypes.byref(split)))
+        return {"variant": int(v[0]), "nthreads": int(v[1]), "r1": int(v[2]), "nstages": int(v[3]),
+                "radix": [int(r) for r in radix[:v[3]]], "split": split.value}
+
     def set_doppler(self, doppler_max, doppler_step, doppler_center=0):
         _check(load().gsdr_acq_set_doppler(self._h, int(doppler_max), int(doppler_step), int(doppler_center)))
 
@@ -452,6 +481,19 @@ class Acquisition:
         out = np.zeros(nblocks * self.nprn, ACQ_RESULT_DTYPE)
         _check(load().gsdr_acq_run_stream(self._h, ring._h, int(first_sample), int(nblocks), int(stamp0), _ptr(out)))
         return out.reshape(nblocks, self.nprn)
+
+    def submit_stream(self, ring, first_sample, nblocks=1, stamp0=0):
+        """gsdr_acq_submit_stream: run_stream without the wait, the results copied back
+        behind the grids (up to two submissions in flight; collect the oldest first)."""
+        _check(load().gsdr_acq_submit_stream(self._h, ring._h, int(first_sample), int(nblocks), int(stamp0)))
+
+    def collect(self):
+        """gsdr_acq_collect: waits for the oldest submission -> structured array
+        [nblocks, nprn] with the shape it was submitted with."""
+        out = np.zeros(int(self.conf.max_blocks) * int(self.conf.max_prns), ACQ_RESULT_DTYPE)
+        nb, npr = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(load().gsdr_acq_collect(self._h, _ptr(out), ctypes.byref(nb), ctypes.byref(npr)))
+        return out[:nb.value * npr.value].reshape(nb.value, npr.value).copy()
 
     def set_step_two(self, num_doppler_bins_step2=4, doppler_step2=125.0, pfa2=0.0):
         """make_two_steps narrow grid (Acq_Conf second_nbins / second_doppler_step /

@@ -249,6 +249,21 @@ void gsdr_acq_destroy(gsdr_acq* acq);
 
 /* Doppler bins D actually used, and the FFT size. */
 int gsdr_acq_get_dims(const gsdr_acq* acq, uint32_t* num_doppler_bins, uint32_t* fft_size);
+/* The FFT plan the handle runs on (for tests and diagnostics; no effect on the engine).
+ * *variant: 1-4 compile-time LDS plans, 10-12 runtime LDS plans on 256 / 512 / 1024
+ * threads, 20 / 22 the generic four-step on 256 / 1024 threads, 24-27 the packed
+ * four-step.  *nthreads: the workgroup size of the variant's kernels.  *r1: the
+ * four-step's register radix R (N = R * N2), 0 for an LDS size.  *nstages and radix[]:
+ * the stages of the LDS plan, or of the N2 sub-plan of a four-step; *nstages = 0 for
+ * the packed four-step's compile-time sub-plans; radix[i] = 1 for i >= *nstages.  Any
+ * output pointer may be null. */
+int gsdr_acq_get_plan(const gsdr_acq* acq, int32_t* variant, int32_t* nthreads, int32_t* r1, int32_t* nstages,
+    int32_t radix[8]);
+/* The split register four-step correlate in effect (0: none): 1 / 25 for 25000 with one /
+ * two PRNs per workgroup (GSDR_ACQ_PPW), 4 / 24 for 100000 with one / two sub-transforms
+ * per workgroup (GSDR_ACQ_QPW), 12 for 32000, 13 for 64000; GSDR_ACQ_SPLIT=0 and
+ * max_dwells > 1 give 0. */
+int gsdr_acq_get_split(const gsdr_acq* acq, int32_t* split);
 
 /* set_local_code for a batch of PRNs (pcps_acquisition.cc:176-209): codes is
  * nprn rows of consumed_samples complex<float> (host); the engine places each in

@@ -66,6 +66,14 @@ def test_null_arguments_are_rejected():
     assert L.gsdr_acq_set_threshold(None, 1.0) == gsdr.GSDR_E_ARG
 
 
+def test_plan_getters_reject_null():
+    L = gsdr.load()
+    split = ctypes.c_int32(7)
+    assert L.gsdr_acq_get_plan(None, None, None, None, None, None) == gsdr.GSDR_E_ARG
+    assert L.gsdr_acq_get_split(None, ctypes.byref(split)) == gsdr.GSDR_E_ARG
+    assert b"null" in L.gsdr_last_error() and split.value == 7
+
+
 def test_create_without_device_fails_cleanly():
     if gsdr.device_count() > 0:
         pytest.skip("a GPU is present; covered by the gpu tests")

@@ -16,45 +16,9 @@ import gsdr
 from gsdr import synth
 from oracle import pcps, replica
 
+from acq_checks import RTOL, _check_result, _codes, _oracle_grids  # noqa: F401 (other test modules import them from here)
+
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-4
-
-
-def _codes(prns, fs, n):
-    return np.stack([synth.gps_ca_sampled(p, fs, n) for p in prns])
-
-
-def _oracle_grids(x, codes, fs, dmax, dstep, D):
-    N = len(x)
-    wipe = pcps.doppler_wipeoffs(fs, N, dmax, dstep, D)
-    grids = []
-    for c in codes:
-        cf = pcps.fft_code(c, N, N)
-        grids.append(pcps.magnitude_grid(x, wipe, cf))
-    return grids
-
-
-def _check_result(r, M, pfa, spc, fs, dmax, dstep, spcode):
-    """Compare one GPU result record with the oracle statistics of grid M."""
-    N = M.shape[1]
-    if pfa > 0:
-        ti, di, gmax, ip, stat = pcps.max_to_input_power_statistic(M)
-    else:
-        ti, di, gmax, second, stat = pcps.first_vs_second_peak_statistic(M, spc, N)
-    same_cell = (r["doppler_index"] == di and r["code_phase"] == ti)
-    if not same_cell:  # near tie (H3)
-        assert abs(M[r["doppler_index"], r["code_phase"]] - gmax) <= RTOL * gmax, (r, ti, di)
-        return False
-    assert abs(r["peak"] - gmax) <= RTOL * gmax
-    assert r["doppler_hz"] == pcps.doppler_hz(di, dmax, dstep)
-    assert r["acq_delay_samples"] == float(np.fmod(np.float32(ti), np.float32(spcode)))
-    if pfa > 0:
-        assert abs(r["input_power"] - ip) <= RTOL * ip
-    else:
-        assert abs(r["second_peak"] - second) <= RTOL * second
-    assert abs(r["test_statistic"] - stat) <= RTOL * stat
-    return True
 
 
 def test_reference_capture_validation(gps_capture):

@@ -9,48 +9,11 @@ import gsdr
 from gsdr import synth
 from oracle import pcps
 
+from acq_checks import RTOL, _check, _oracle_attempt  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-4
 FS, C = 4000000, 4000
-
-
-def _oracle_attempt(chunks, codes, pfa, D, dmax, dstep, bit_transition, spc, threshold, fs=FS):
-    """Per PRN: (dwell index, ti, di, peak, input_power/second, stat) of the decision."""
-    N = len(chunks[0])
-    wipe = pcps.doppler_wipeoffs(fs, N, dmax, dstep, D)
-    out = []
-    for code in codes:
-        cf = pcps.fft_code(code, N, N, bit_transition=bit_transition)
-        acc = None
-        for k, x in enumerate(chunks):
-            M = pcps.magnitude_grid(x, wipe, cf, bit_transition=bit_transition)
-            acc = M if acc is None else (acc + M).astype(np.float32)
-            if pfa > 0:
-                ti, di, peak, ip, stat = pcps.max_to_input_power_statistic(acc, k + 1)
-                aux = ip
-            else:
-                full = np.zeros((D, N), np.float32)
-                full[:, :acc.shape[1]] = acc
-                ti, di, peak, aux, stat = pcps.first_vs_second_peak_statistic(full, spc, N)
-            if stat > threshold or k + 1 == len(chunks):
-                out.append((k, ti, di, peak, aux, stat, acc))
-                break
-    return out
-
-
-def _check(r, o, pfa):
-    k, ti, di, peak, aux, stat, acc = o
-    assert r["num_dwells"] == k + 1
-    if (r["doppler_index"], r["code_phase"]) != (di, ti):  # near tie (SURVEY §7 H3)
-        assert abs(acc[r["doppler_index"], r["code_phase"]] - peak) <= RTOL * peak
-        return
-    assert abs(r["peak"] - peak) <= RTOL * peak
-    assert abs(r["test_statistic"] - stat) <= RTOL * stat
-    if pfa > 0:
-        assert abs(r["input_power"] - aux) <= RTOL * aux
-    else:
-        assert abs(r["second_peak"] - aux) <= RTOL * aux
 
 
 @pytest.mark.parametrize("pfa", [0.01, 0.0])
@@ -178,3 +141,104 @@ def test_noncoherent_dwells_four_step(pfa):
         _check(res[0, i], orc[i], pfa)
         assert res[0, i]["samplestamp"] == 7 + orc[i][0] * C
         assert res[0, i]["positive"] == int(orc[i][5] > thr)
+
+
+# ---------------------------------------------------------------- off the benchmark sizes
+# 6 Msps: FFT 12000 with bit transition (runtime LDS plan, 1024 threads) and 6000 for the
+# dwells (512 threads); 40000 = 25 x 1600 on the generic four-step (256 threads): 20 Msps
+# with bit transition, 40 Msps for the dwells and the integer inputs.
+OFF_GRID = (1000, 250)  # +-1000 Hz / 250 Hz: 8 Doppler rows
+
+
+def _gps_case(fs, n_samples, seed, cn0):
+    sats = synth.random_constellation(3, seed_offset=seed, cn0_dbhz=cn0, max_doppler=900.0)
+    x = synth.gps_l1_iq(fs, n_samples, sats, seed_offset=seed)
+    vis = [s.prn for s in sats]
+    prns = np.array(vis + [next(p for p in range(1, 33) if p not in vis)])
+    return x, prns
+
+
+@pytest.mark.parametrize("pfa", [0.01, 0.0])
+@pytest.mark.parametrize("fs,variant,nthreads", [(6000000, 12, 1024), (20000000, 20, 256)])
+def test_bit_transition_other_rates(fs, variant, nthreads, pfa):
+    """bit_transition_flag at 6 / 20 Msps: FFT 12000 / 40000 with the code in the second
+    half and outputs [N/2, N), two attempts."""
+    C, (dmax, dstep), nb = fs // 1000, OFF_GRID, 2
+    x, prns = _gps_case(fs, nb * 2 * C, 300 + fs // 1000000, 47.0)
+    codes = np.stack([np.resize(synth.gps_ca_sampled(int(p), fs), 2 * C) for p in prns])
+    acq = gsdr.Acquisition(fs, 2 * C, dmax, dstep, pfa=pfa, max_prns=len(prns), max_blocks=nb, bit_transition=True)
+    plan = acq.plan
+    assert acq.fft_size == 2 * C and (plan["variant"], plan["nthreads"], plan["split"]) == (variant, nthreads, 0), plan
+    acq.set_local_codes(codes, prns)
+    D = acq.num_doppler_bins
+    spc = int(np.ceil(fs / 1023000.0))
+    thr = pcps.threshold(pfa, 2 * C, D, 1, bit_transition=True) if pfa > 0 else 2.0
+    if pfa > 0:
+        assert abs(acq.threshold - thr) <= 1e-6 * thr
+    else:
+        acq.set_threshold(thr)
+    res = acq.run(x, nblocks=nb)
+    for b in range(nb):
+        chunk = x[b * 2 * C:(b + 1) * 2 * C]
+        orc = _oracle_attempt([chunk], codes, pfa, D, dmax, dstep, True, spc, thr, fs=fs)
+        for i in range(len(prns)):
+            _check(res[b, i], orc[i], pfa)
+            assert res[b, i]["samplestamp"] == b * 2 * C
+            assert res[b, i]["positive"] == int(orc[i][5] > thr)
+
+
+@pytest.mark.parametrize("pfa", [0.01, 0.0])
+@pytest.mark.parametrize("fs,variant,nthreads", [(6000000, 11, 512), (40000000, 20, 256)])
+def test_noncoherent_dwells_other_rates(fs, variant, nthreads, pfa):
+    """max_dwells = 2 at N = 6000 (runtime LDS plan) and 40000 (generic four-step): the
+    accumulating general path, two attempts."""
+    C, K, nat, (dmax, dstep) = fs // 1000, 2, 2, OFF_GRID
+    x, prns = _gps_case(fs, nat * K * C, 310 + fs // 1000000, 46.0)
+    codes = np.stack([synth.gps_ca_sampled(int(p), fs) for p in prns])
+    acq = gsdr.Acquisition(fs, C, dmax, dstep, pfa=pfa, max_prns=len(prns), max_blocks=nat, max_dwells=K)
+    plan = acq.plan
+    assert acq.fft_size == C and (plan["variant"], plan["nthreads"], plan["split"]) == (variant, nthreads, 0), plan
+    acq.set_local_codes(codes, prns)
+    D = acq.num_doppler_bins
+    spc = int(np.ceil(fs / 1023000.0))
+    thr = pcps.threshold(pfa, C, D, K) if pfa > 0 else 3.0
+    if pfa > 0:
+        assert abs(acq.threshold - thr) <= 1e-6 * thr
+    else:
+        acq.set_threshold(thr)
+    res = acq.run(x, nblocks=nat, stamp0=100)
+    used = set()
+    for a in range(nat):
+        chunks = [x[(a * K + k) * C:(a * K + k + 1) * C] for k in range(K)]
+        orc = _oracle_attempt(chunks, codes, pfa, D, dmax, dstep, False, spc, thr, fs=fs)
+        for i in range(len(prns)):
+            _check(res[a, i], orc[i], pfa)
+            assert res[a, i]["samplestamp"] == 100 + (a * K + orc[i][0]) * C
+            assert res[a, i]["positive"] == int(orc[i][5] > thr)
+            used.add(int(res[a, i]["num_dwells"]))
+    assert used == {1, 2}  # decisions at the first dwell and at the last
+
+
+@pytest.mark.parametrize("item", [gsdr.ITEM_CSHORT, gsdr.ITEM_IBYTE])
+def test_integer_input_generic_four_step(item):
+    """cshort / ibyte input at N = 40000 (generic four-step): the engine converts the
+    interleaved integer pairs exactly, so the records are byte-identical to the
+    gr_complex run of the converted samples, which is checked against the oracle."""
+    fs, N, (dmax, dstep), pfa = 40000000, 40000, OFF_GRID, 0.01
+    x, prns = _gps_case(fs, N, 340 + item, 50.0)
+    xi = synth.to_cshort(x, 2000.0) if item == gsdr.ITEM_CSHORT else synth.to_ibyte(x, 24.0)
+    xf = (xi[0::2].astype(np.float32) + 1j * xi[1::2].astype(np.float32)).astype(np.complex64)
+    codes = np.stack([synth.gps_ca_sampled(int(p), fs) for p in prns])
+    acq = gsdr.Acquisition(fs, N, dmax, dstep, pfa=pfa, max_prns=len(prns), item_type=item)
+    assert acq.plan["variant"] == 20
+    acq.set_local_codes(codes, prns)
+    res = acq.run(xi)[0]
+    ref = gsdr.Acquisition(fs, N, dmax, dstep, pfa=pfa, max_prns=len(prns))
+    ref.set_local_codes(codes, prns)
+    res_f = ref.run(xf)[0]
+    assert res.tobytes() == res_f.tobytes()
+    orc = _oracle_attempt([xf], codes, pfa, acq.num_doppler_bins, dmax, dstep, False, int(np.ceil(fs / 1023000.0)),
+                          acq.threshold, fs=fs)
+    for i in range(len(prns)):
+        _check(res[i], orc[i], pfa)
+        assert res[i]["positive"] == int(orc[i][5] > acq.threshold)

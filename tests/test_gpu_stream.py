@@ -314,3 +314,94 @@ def test_submit_collect_matches_contiguous():
         assert len(g) == len(r) and len(g) >= ms - 2, (c, len(g), len(r))
         assert g.tobytes() == r.tobytes(), c
     ring.close()
+
+
+@pytest.mark.parametrize("change", ["active_prns", "local_code"])
+def test_acq_submit_collect_two_in_flight(change):
+    """gsdr_acq_submit_stream / gsdr_acq_collect with two submissions in flight on one ring:
+    4 blocks x 4 PRNs, then -- after gsdr_acq_set_active_prns(2), or one slot's code replaced
+    by gsdr_acq_set_local_code -- a later stretch of another shape.  Collected oldest first,
+    each with the shape and the active set of its submission and records byte-identical to
+    gsdr_acq_run of the same samples with that set; a third submission in flight and a
+    collect with nothing submitted are refused with GSDR_E_STATE."""
+    nb = 4
+    sats = synth.random_constellation(4, seed_offset=41, cn0_dbhz=47.0)
+    x = synth.gps_l1_iq(FS, 8 * N, sats, seed_offset=41)
+    prns = np.array([s.prn for s in sats])
+    codes = np.stack([synth.gps_ca_sampled(s.prn, FS) for s in sats])
+    other = next(p for p in range(1, 33) if p not in prns)
+    acq = gsdr.Acquisition(FS, N, 10000, 250, pfa=0.01, max_prns=4, max_blocks=nb)
+    acq.set_local_codes(codes, prns)
+    ref = gsdr.Acquisition(FS, N, 10000, 250, pfa=0.01, max_prns=4, max_blocks=nb)
+    ref.set_local_codes(codes, prns)
+    ring = gsdr.Stream(gsdr.ITEM_GR_COMPLEX, capacity_items=16 * N, max_window_items=8 * N)
+    ring.push(x[:5 * N], 0)
+    ring.push(x[5 * N:], 5 * N)
+    with pytest.raises(gsdr.GsdrError) as e:
+        acq.collect()
+    assert e.value.code == gsdr.GSDR_E_STATE
+    acq.submit_stream(ring, 0, nblocks=4, stamp0=1000)
+    want_first = ref.run(x[:4 * N], nblocks=4, stamp0=1000)
+    if change == "active_prns":
+        acq.set_active_prns(2)
+        ref.set_active_prns(2)
+        shape2 = (3, 2)
+    else:
+        acq.set_local_code(1, synth.gps_ca_sampled(other, FS), other)
+        ref.set_local_code(1, synth.gps_ca_sampled(other, FS), other)
+        shape2 = (3, 4)
+    acq.submit_stream(ring, 4 * N + 123, nblocks=3, stamp0=4 * N + 123)
+    want_second = ref.run(x[4 * N + 123:7 * N + 123], nblocks=3, stamp0=4 * N + 123)
+    with pytest.raises(gsdr.GsdrError) as e:
+        acq.submit_stream(ring, 0, nblocks=1)
+    assert e.value.code == gsdr.GSDR_E_STATE
+    first = acq.collect()
+    assert first.shape == (4, 4) and list(first[0]["prn"]) == list(prns)
+    assert first.tobytes() == want_first.tobytes()
+    second = acq.collect()
+    assert second.shape == shape2 == want_second.shape
+    if change == "local_code":
+        assert list(second[0]["prn"]) == [prns[0], other, prns[2], prns[3]]
+    assert second.tobytes() == want_second.tobytes()
+    with pytest.raises(gsdr.GsdrError) as e:
+        acq.collect()
+    assert e.value.code == gsdr.GSDR_E_STATE
+    # the slots are free again
+    acq.submit_stream(ring, N, nblocks=1, stamp0=N)
+    assert acq.collect().tobytes() == ref.run(x[N:2 * N], nblocks=1, stamp0=N).tobytes()
+    ring.close()
+    acq.close()
+    ref.close()
+
+
+def test_landed_and_wait_landed():
+    """gsdr_stream_landed never decreases over a sequence of pushes and never passes the
+    head; gsdr_stream_wait_landed(head) returns with everything landed, after which
+    gsdr_stream_read gives exactly the pushed items (the source arrays are overwritten
+    first: only device memory can hold them).  Waiting beyond the head is no error: it waits
+    for every pending push and returns (stream.cpp land_locked), the landed index stays at
+    the head."""
+    rng = np.random.default_rng(43)
+    sizes = (1, 1000, 4096, 3 * N - 97, 2 * N + 1000, N - 1000)
+    total = sum(sizes)
+    x = (rng.standard_normal(total) + 1j * rng.standard_normal(total)).astype(np.complex64)
+    ring = gsdr.Stream(gsdr.ITEM_GR_COMPLEX, capacity_items=8 * N, max_window_items=4 * N)
+    origin, head, last = 500, 500, 0
+    for n in sizes:
+        src = x[head - origin:head - origin + n].copy()
+        ring.push(src, head)
+        head += n
+        seen = ring.landed()
+        assert last <= seen <= head
+        last = seen
+        if n == 4096:  # a wait in the middle of the sequence
+            assert ring.wait_landed(head) == head
+            last = head
+            src[:] = 0  # landed: the caller's buffer is free again
+    assert head == origin + total
+    assert ring.wait_landed(head) >= head
+    assert ring.landed() == head
+    assert ring.wait_landed(head + 12345) == head
+    got = ring.read(origin, total)
+    assert got.tobytes() == x.tobytes()
+    ring.close()
