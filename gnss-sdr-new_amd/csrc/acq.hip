@@ -15,110 +15,153 @@
 //                     Gnss_Synchro fields                                (:511-543, :697-713)
 //   K_second          per (b,p), peak-ratio mode only: recompute row d*, second peak outside
 //                     the +-1 chip window with the reference's wrap      (:546-612)
-#include "acq_impl.h"
-
+//
+// This unit is the C ABI.  The kernels are in acq_kernels.h / acq_split_kernels.h
+// (templates) and acq_common.hip, the launch sequences in acq_launch.h.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
-#include <string>
+#include <memory>
+#include <new>
 #include <utility>
+
+#include "acq_handle.h"
+#include "acq_plans.h"
 #include "gsdr_stream_internal.h"
+
+using namespace gsdr_acq_impl;
 
 namespace
 {
 
-// op: 0 run, 1 code fft, 2 dump spectra, 3 dump grid, 4 set attributes
-int dispatch(gsdr_acq* a, int op, const void* iq, uint32_t nblocks, uint64_t stride, uint64_t stamp0,
-    gsdr_acq_result* res, hipStream_t s, uint32_t aux)
+int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op)
 {
-    // the forward-spectrum layout of these launches: the main grid's (XMap), or the
-    // plain one when a narrow step-two grid has replaced the wipe-off rows
-    a->xm = (a->st2.active || a->d_wipe != a->d_wipe_grid) ? XMap{a->D, 0u, a->N} : a->xm_grid;
-    if (a->variant >= 20) return gsdr_acq_impl::dispatch_four(a, op, iq, nblocks, stride, stamp0, res, s, aux);
-    if (a->variant >= 10) return gsdr_acq_impl::dispatch_runtime(a, op, iq, nblocks, stride, stamp0, res, s, aux);
-    return gsdr_acq_impl::dispatch_static(a, op, iq, nblocks, stride, stamp0, res, s, aux);
+    if (a->variant >= 20) return dispatch_four(a, v, op);
+    if (a->variant >= 10) return dispatch_runtime(a, v, op);
+    return dispatch_static(a, v, op);
+}
+
+// AcqOp::Run of nblocks blocks at iq (device), results to res (device).
+int run_blocks(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, uint64_t stamp0,
+    gsdr_acq_result* res, hipStream_t s)
+{
+    return dispatch(a, v, AcqOp{AcqOp::Run, iq, nblocks, stride, stamp0, res, s});
+}
+
+// The same on the ring's samples from first_sample, into d_res on the handle's stream.
+int run_ring(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0)
+{
+    gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
+    const void* iq = nullptr;
+    int rc = rd.view(first_sample, (uint64_t)nblocks * a->K * a->consumed, &iq);
+    if (rc == GSDR_OK) rc = rd.acquire(a->stream);
+    if (rc == GSDR_OK) rc = run_blocks(a, view_of(a), iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
+    if (rc == GSDR_OK) rc = rd.release(a->stream);
+    return rc;
+}
+
+// The first n records of d_res to the host, once the handle's stream has produced them.
+int read_results(gsdr_acq* a, gsdr_acq_result* out, size_t n)
+{
+    GSDR_HIP(hipMemcpyAsync(out, a->d_res, n * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost, a->stream));
+    GSDR_HIP(hipStreamSynchronize(a->stream));
+    return GSDR_OK;
+}
+
+int code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
+{
+    AcqOp op{AcqOp::CodeFft};
+    op.first_slot = first_slot;
+    op.nslots = nslots;
+    return dispatch(a, view_of(a), op);
+}
+
+// update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), float arithmetic:
+// the nb frequencies of a narrow grid around center
+void step_two_freqs(const gsdr_acq* a, float center, float* freqs)
+{
+    const uint32_t nb = a->st2.nbins;
+    const float half = (float)std::floor((double)nb / 2.0);
+    for (uint32_t d = 0; d < nb; ++d)
+        {
+            volatile float dop = ((float)d - half) * a->st2.step;
+            freqs[d] = center + dop;
+        }
+}
+
+// The table W_n^m = exp(-2 pi i m / n), m < n, in double, rounded once.
+hipError_t upload_twiddles(float2* d_tw, uint32_t n)
+{
+    std::vector<float2> tw(n);
+    for (uint32_t m = 0; m < n; ++m)
+        {
+            const double ang = 2.0 * M_PI * (double)m / (double)n;
+            tw[m] = make_float2((float)std::cos(ang), (float)(-std::sin(ang)));
+        }
+    return hipMemcpy(d_tw, tw.data(), (size_t)n * sizeof(float2), hipMemcpyHostToDevice);
 }
 
 // Pick a compile-time plan when one matches N, else the smallest workgroup that
-// admits a runtime plan.
+// admits a runtime plan, else a four-step plan (acq_plans.h).
 constexpr size_t kLdsBytes = 160 * 1024;
+
+void set_four(gsdr_acq* a, int id, int nt, int r1, const Plan& sub)
+{
+    a->variant = id;
+    a->nt = nt;
+    a->plan4 = gsdr::fft::Plan4{};
+    a->plan4.n = (int)a->N;
+    a->plan4.r1 = r1;
+    a->plan4.sub = sub;
+    a->plan.n = (int)a->N;  // buffer sizes
+}
 
 bool choose_variant(gsdr_acq* a)
 {
     const int N = (int)a->N;
-    struct S
-    {
-        int id, n, nt;
-        gsdr::fft::Plan p;
-    };
-    const S statics[] = {
-        {1, StaticPlan<256, 20, 20, 10>::N, 256, StaticPlan<256, 20, 20, 10>::plan()},
-        {2, StaticPlan<512, 20, 20, 20>::N, 512, StaticPlan<512, 20, 20, 20>::plan()},
-        {3, StaticPlan<1024, 16, 10, 10, 10>::N, 1024, StaticPlan<1024, 16, 10, 10, 10>::plan()},
-        {4, StaticPlan<256, 20, 10, 10>::N, 256, StaticPlan<256, 20, 10, 10>::plan()},
-    };
-    for (const S& st : statics)
-        if (st.n == N)
-            {
-                a->variant = st.id;
-                a->nt = st.nt;
-                a->plan = st.p;
-                return true;
-            }
-    const int ids[] = {10, 11, 12};
-    const int nts[] = {256, 512, 1024};
-    for (int i = 0; i < 3; ++i)
-        if (gsdr::fft::make_plan(N, nts[i], a->plan) && a->plan.nstages >= 2 &&
-            (size_t)N * sizeof(float2) + 16 * sizeof(RowStat) <= kLdsBytes)
-            {
-                a->variant = ids[i];
-                a->nt = nts[i];
-                return true;
-            }
-    // packed four-step (FourStepPkPlan) for the sizes of the GNSS configurations
-    // beyond one workgroup's LDS: Galileo E1 4 / 8 ms at 8 Msps, 4 ms at 25 Msps,
-    // 1 ms at 25 Msps (GSDR_ACQ_FOUR_GENERIC=1 keeps the generic four-step)
-    {
-        struct F
-        {
-            int id, n, r, n2;
-        };
-        const F fours[] = {{24, 32000, 8, 4000}, {25, 64000, 16, 4000}, {26, 100000, 25, 4000}, {27, 25000, 5, 5000}};
-        const char* g = std::getenv("GSDR_ACQ_FOUR_GENERIC");
-        for (const F& f : fours)
-            if (f.n == N && !(g && std::atoi(g) != 0))
-                {
-                    a->variant = f.id;
-                    a->nt = 256;
-                    a->plan4 = gsdr::fft::Plan4{};
-                    a->plan4.n = N;
-                    a->plan4.r1 = f.r;
-                    a->plan4.sub.n = f.n2;
-                    a->plan4.sub.nstages = 0;  // compile-time sub-plan
-                    a->plan.n = N;
-                    return true;
-                }
-    }
+    const auto fits = [](int n) { return (size_t)n * sizeof(float2) + 16 * sizeof(RowStat) <= kLdsBytes; };
+    if (find_plan(StaticPlans{}, [&](auto e) {
+            using PT = typename decltype(e)::type;
+            if (PT::N != N) return false;
+            a->variant = e.id;
+            a->nt = PT::NT;
+            a->plan = PT::plan();
+            return true;
+        }))
+        return true;
+    if (find_plan(RuntimePlans{}, [&](auto e) {
+            using PT = typename decltype(e)::type;
+            if (!gsdr::fft::make_plan(N, PT::NT, a->plan) || a->plan.nstages < 2 || !fits(N)) return false;
+            a->variant = e.id;
+            a->nt = PT::NT;
+            return true;
+        }))
+        return true;
+    // the packed four-step at its sizes
+    if (!a->env.four_generic && find_plan(FourPkPlans{}, [&](auto e) {
+            using PT = typename decltype(e)::type;
+            if (PT::N != N) return false;
+            Plan sub{};
+            sub.n = PT::N2;
+            sub.nstages = 0;  // compile-time sub-plan
+            set_four(a, e.id, PT::NT, PT::R, sub);
+            return true;
+        }))
+        return true;
     // four-step (fft_4step.h): N = R * N2, the largest register radix R whose N2
     // has an LDS plan
     const int radices[] = {25, 20, 16, 12, 10, 8};
     for (int R : radices)
         {
-            if (N % R != 0) continue;
-            const int N2 = N / R;
-            if ((size_t)N2 * sizeof(float2) + 16 * sizeof(RowStat) > kLdsBytes) continue;
-            for (int i = 0; i < 3; i += 2)  // 256 or 1024 threads (variants 20, 22)
-                {
+            if (N % R != 0 || !fits(N / R)) continue;
+            if (find_plan(FourPlans{}, [&](auto e) {
+                    using PT = typename decltype(e)::type;
                     Plan sub{};
-                    if (!gsdr::fft::make_plan(N2, nts[i], sub) || sub.nstages < 2) continue;
-                    a->variant = 20 + i;
-                    a->nt = nts[i];
-                    a->plan4 = gsdr::fft::Plan4{};
-                    a->plan4.n = N;
-                    a->plan4.r1 = R;
-                    a->plan4.sub = sub;
-                    a->plan.n = N;  // buffer sizes
+                    if (!gsdr::fft::make_plan(N / R, PT::NT, sub) || sub.nstages < 2) return false;
+                    set_four(a, e.id, PT::NT, R, sub);
                     return true;
-                }
+                }))
+                return true;
         }
     return false;
 }
@@ -146,6 +189,7 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
 
     gsdr_acq* a = new (std::nothrow) gsdr_acq();
     GSDR_REQUIRE(a, GSDR_E_ALLOC, "gsdr_acq_create: out of host memory");
+    std::unique_ptr<gsdr_acq, void (*)(gsdr_acq*)> guard(a, gsdr_acq_destroy);  // until *out takes it
     a->device = device;
     a->conf = *conf;
     if (a->conf.max_dwells == 0) a->conf.max_dwells = 1;
@@ -154,31 +198,18 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
     if (a->conf.bit_transition_flag) a->conf.max_dwells = 1;
     a->K = a->conf.max_dwells;
     a->consumed = conf->consumed_samples;
-    if (const char* w = std::getenv("GSDR_ACQ_WIPE"))
-        {
-            const std::string m(w);
-            a->wipe_mode = m == "generic" ? GSDR_WIPE_GENERIC : (m == "avx2" ? GSDR_WIPE_AVX2 : GSDR_WIPE_EXACT);
-        }
+    a->env = read_acq_env();
+    a->wipe_mode = a->env.wipe_mode;
     // pcps_acquisition.cc:85-92
     uint32_t N = conf->fft_size;
     if (N == 0) N = (conf->sampled_ms == conf->ms_per_code || conf->sampled_ms == 0) ? a->consumed : 2 * a->consumed;
-    if (N < a->consumed)
-        {
-            delete a;
-            gsdr::set_error("gsdr_acq_create: fft_size %u < consumed_samples %u", N, a->consumed);
-            return GSDR_E_ARG;
-        }
+    GSDR_REQUIRE(N >= a->consumed, GSDR_E_ARG, "gsdr_acq_create: fft_size %u < consumed_samples %u", N, a->consumed);
     a->N = N;
     a->lead = N - a->consumed;
     a->eff = N;
     if (conf->bit_transition_flag)
         {
-            if (N % 2 != 0)
-                {
-                    delete a;
-                    gsdr::set_error("gsdr_acq_create: bit_transition_flag needs an even fft_size (%u)", N);
-                    return GSDR_E_ARG;
-                }
+            GSDR_REQUIRE(N % 2 == 0, GSDR_E_ARG, "gsdr_acq_create: bit_transition_flag needs an even fft_size (%u)", N);
             a->lead = N / 2;
             a->eff = N / 2;
         }
@@ -186,49 +217,29 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
     a->D = conf->num_doppler_bins;
     if (a->D == 0)
         a->D = (uint32_t)std::ceil((double)(conf->doppler_max - (-conf->doppler_max)) / (double)conf->doppler_step);
-    if (a->D == 0)
-        {
-            delete a;
-            gsdr::set_error("gsdr_acq_create: zero Doppler bins");
-            return GSDR_E_ARG;
-        }
+    GSDR_REQUIRE(a->D != 0, GSDR_E_ARG, "gsdr_acq_create: zero Doppler bins");
     const bool ok = choose_variant(a);
     const bool four = a->variant >= 20;
     a->lds_bytes = (size_t)(four ? a->plan4.sub.n : N) * sizeof(float2) + 16 * sizeof(RowStat);
-    if (!ok || a->lds_bytes > kLdsBytes)
-        {
-            delete a;
-            gsdr::set_error("gsdr_acq_create: FFT size %u not supported (needs 2^a*3^b*5^c; up to 20352 points in "
-                            "LDS, larger sizes as R*N2 with R in {8,10,12,16,20,25} and N2 <= 20352)", N);
-            return GSDR_E_UNSUPPORTED;
-        }
-    int rc = dispatch(a, 4, nullptr, 0, 0, 0, nullptr, nullptr, 0);
-    if (rc == GSDR_OK && four) rc = gsdr_acq_impl::setup_split(a);
+    GSDR_REQUIRE(ok && a->lds_bytes <= kLdsBytes, GSDR_E_UNSUPPORTED,
+        "gsdr_acq_create: FFT size %u not supported (needs 2^a*3^b*5^c; up to 20352 points in LDS, larger sizes as "
+        "R*N2 with R in {8,10,12,16,20,25} and N2 <= 20352)", N);
+    int rc = dispatch(a, view_of(a), AcqOp{AcqOp::SetAttrs});
+    if (rc == GSDR_OK && four) rc = setup_split(a);
     if (rc == GSDR_OK && !a->general && default_pk_variant(N) > 0)
-        {
-            int v = default_pk_variant(N);
-            if (const char* e = std::getenv("GSDR_ACQ_CORR_VARIANT")) v = std::atoi(e);
-            rc = gsdr_acq_impl::setup_corr_variant(a, v);
-        }
-    if (rc != GSDR_OK)
-        {
-            delete a;
-            return rc;
-        }
+        rc = setup_corr_variant(a, a->env.corr_variant >= 0 ? a->env.corr_variant : default_pk_variant(N));
+    if (rc != GSDR_OK) return rc;
     const size_t nP = conf->max_prns, nB = conf->max_blocks;
     hipError_t e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
-
-    const size_t tw_n = N;
-    if (e == hipSuccess) e = hipMalloc(&a->d_tw, tw_n * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc(&a->d_tw, (size_t)N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_wipe, (size_t)a->D * N * sizeof(float2));
-    a->d_wipe_grid = a->d_wipe;
     if (e == hipSuccess) e = hipMalloc(&a->d_code_fft, nP * N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_code_stage, nP * a->consumed * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_prn, nP * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&a->d_X, nB * a->K * a->D * N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_stats, nB * nP * a->K * a->D * sizeof(RowStat));
     if (e == hipSuccess) e = hipMalloc(&a->d_res, nB * nP * sizeof(gsdr_acq_result));
-    if (e == hipSuccess) e = hipMalloc(&a->d_iq, nB * a->K * a->consumed * item_bytes(conf->item_type));
+    if (e == hipSuccess) e = hipMalloc(&a->d_iq, nB * a->K * a->consumed * gsdr::item_bytes(conf->item_type));
     if (a->general)
         {
             // accumulation rows held by running workgroups only: the chip's resident
@@ -263,48 +274,18 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
             if (e == hipSuccess) e = hipMalloc(&a->d_scratch, (size_t)nslots * N * sizeof(float2));
             if (e == hipSuccess) e = hipMalloc(&a->d_slots, (size_t)a->plan4.nwords * sizeof(uint32_t));
             if (e == hipSuccess) e = hipMemset(a->d_slots, 0, (size_t)a->plan4.nwords * sizeof(uint32_t));
-            if (e == hipSuccess)
-                {
-                    const int N2 = a->plan4.sub.n;
-                    std::vector<float2> t2(N2);
-                    for (int m = 0; m < N2; ++m)
-                        {
-                            const double ang = 2.0 * M_PI * (double)m / (double)N2;
-                            t2[m] = make_float2((float)std::cos(ang), (float)(-std::sin(ang)));
-                        }
-                    e = hipMemcpy(a->d_tw_sub, t2.data(), N2 * sizeof(float2), hipMemcpyHostToDevice);
-                }
+            if (e == hipSuccess) e = upload_twiddles(a->d_tw_sub, (uint32_t)a->plan4.sub.n);
             a->plan4.tw_sub = a->d_tw_sub;
             a->plan4.scratch = a->d_scratch;
             a->plan4.slots = a->d_slots;
         }
-    if (e != hipSuccess)
-        {
-            gsdr::set_error("gsdr_acq_create: device allocation failed: %s", hipGetErrorString(e));
-            gsdr_acq_destroy(a);
-            return GSDR_E_ALLOC;
-        }
-    // twiddles W_N^m in double, rounded once
-    std::vector<float2> tw(tw_n);
-    for (uint32_t m = 0; m < N; ++m)
-        {
-            const double ang = 2.0 * M_PI * (double)m / (double)N;
-            tw[m] = make_float2((float)std::cos(ang), (float)(-std::sin(ang)));
-        }
-    if ((e = hipMemcpy(a->d_tw, tw.data(), tw_n * sizeof(float2), hipMemcpyHostToDevice)) != hipSuccess)
-        {
-            gsdr::set_error("gsdr_acq_create: twiddle upload: %s", hipGetErrorString(e));
-            gsdr_acq_destroy(a);
-            return GSDR_E_DEVICE;
-        }
+    GSDR_REQUIRE(e == hipSuccess, GSDR_E_ALLOC, "gsdr_acq_create: device allocation failed: %s", hipGetErrorString(e));
+    e = upload_twiddles(a->d_tw, N);
+    GSDR_REQUIRE(e == hipSuccess, GSDR_E_DEVICE, "gsdr_acq_create: twiddle upload: %s", hipGetErrorString(e));
     rc = rebuild_wipeoffs(a);
-    if (rc != GSDR_OK)
-        {
-            gsdr_acq_destroy(a);
-            return rc;
-        }
+    if (rc != GSDR_OK) return rc;
     compute_threshold(a);
-    *out = a;
+    *out = guard.release();
     return GSDR_OK;
 }
 
@@ -373,7 +354,7 @@ int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* pr
     GSDR_HIP(hipMemcpyAsync(a->d_code_stage, codes, (size_t)nprn * a->consumed * sizeof(float2),
         hipMemcpyHostToDevice, a->stream));
     GSDR_HIP(hipMemcpyAsync(a->d_prn, prn, nprn * sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 1, nullptr, 0, 0, 0, nullptr, nullptr, nprn);
+    int rc = code_fft(a, 0, nprn);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
     a->nprn = nprn;
@@ -383,7 +364,7 @@ int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* pr
 int gsdr_acq_set_local_code(gsdr_acq* a, uint32_t slot, const float* code, uint32_t prn)
 {
     GSDR_REQUIRE(a && code, GSDR_E_ARG, "gsdr_acq_set_local_code: null argument");
-    GSDR_REQUIRE(slot < a->conf.max_prns && slot < 0xffffu, GSDR_E_ARG, "gsdr_acq_set_local_code: slot %u outside [0,%u)",
+    GSDR_REQUIRE(slot < a->conf.max_prns, GSDR_E_ARG, "gsdr_acq_set_local_code: slot %u outside [0,%u)",
         slot, a->conf.max_prns);
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
@@ -392,7 +373,7 @@ int gsdr_acq_set_local_code(gsdr_acq* a, uint32_t slot, const float* code, uint3
     GSDR_HIP(hipMemcpyAsync(a->d_code_stage + (size_t)slot * a->consumed, code, (size_t)a->consumed * sizeof(float2),
         hipMemcpyHostToDevice, a->stream));
     GSDR_HIP(hipMemcpyAsync(a->d_prn + slot, &prn, sizeof(uint32_t), hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 1, nullptr, 0, 0, 0, nullptr, nullptr, (slot << 16) | 1u);
+    int rc = code_fft(a, slot, 1);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
     if (a->nprn <= slot) a->nprn = slot + 1;
@@ -441,8 +422,8 @@ int gsdr_acq_set_wipeoff(gsdr_acq* a, int mode)
 int gsdr_acq_get_spectrum_reuse(const gsdr_acq* a, uint32_t* q, uint32_t* p)
 {
     GSDR_REQUIRE(a, GSDR_E_ARG, "gsdr_acq_get_spectrum_reuse: null handle");
-    if (q) *q = a->xm_grid.q;
-    if (p) *p = a->xm_grid.p;
+    if (q) *q = a->xm.q;
+    if (p) *p = a->xm.p;
     return GSDR_OK;
 }
 
@@ -472,7 +453,7 @@ int gsdr_acq_run_device(gsdr_acq* a, const void* iq_dev, uint32_t nblocks, uint6
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     hipStream_t s = stream ? (hipStream_t)stream : a->stream;
-    return dispatch(a, 0, iq_dev, nblocks, stride, stamp0, out_dev, s, 0);
+    return run_blocks(a, view_of(a), iq_dev, nblocks, stride, stamp0, out_dev, s);
 }
 
 int gsdr_acq_run(gsdr_acq* a, const void* iq_host, uint32_t nblocks, uint64_t stamp0, gsdr_acq_result* out)
@@ -483,14 +464,11 @@ int gsdr_acq_run(gsdr_acq* a, const void* iq_host, uint32_t nblocks, uint64_t st
         nblocks, a->conf.max_blocks);
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
-    const size_t bytes = (size_t)nblocks * a->K * a->consumed * item_bytes(a->conf.item_type);
+    const size_t bytes = (size_t)nblocks * a->K * a->consumed * gsdr::item_bytes(a->conf.item_type);
     GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, bytes, hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 0, a->d_iq, nblocks, a->consumed, stamp0, a->d_res, a->stream, 0);
+    int rc = run_blocks(a, view_of(a), a->d_iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
     if (rc != GSDR_OK) return rc;
-    GSDR_HIP(hipMemcpyAsync(out, a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost,
-        a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    return read_results(a, out, (size_t)nblocks * a->nprn);
 }
 
 int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0,
@@ -507,22 +485,9 @@ int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, u
         "gsdr_acq_run_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring), a->device);
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
-    {
-        gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-        const void* iq = nullptr;
-        int rc = rd.view(first_sample, (uint64_t)nblocks * a->K * a->consumed, &iq);
-        if (rc != GSDR_OK) return rc;
-        rc = rd.acquire(a->stream);
-        if (rc != GSDR_OK) return rc;
-        rc = dispatch(a, 0, iq, nblocks, a->consumed, stamp0, a->d_res, a->stream, 0);
-        if (rc != GSDR_OK) return rc;
-        rc = rd.release(a->stream);
-        if (rc != GSDR_OK) return rc;
-    }
-    GSDR_HIP(hipMemcpyAsync(out, a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost,
-        a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    int rc = run_ring(a, ring, first_sample, nblocks, stamp0);
+    if (rc != GSDR_OK) return rc;
+    return read_results(a, out, (size_t)nblocks * a->nprn);
 }
 
 int gsdr_acq_submit_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0)
@@ -547,18 +512,8 @@ int gsdr_acq_submit_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample
                 (size_t)a->conf.max_blocks * a->conf.max_prns * sizeof(gsdr_acq_result), hipHostMallocDefault));
             GSDR_HIP(hipEventCreateWithFlags(&a->sub_done[slot], hipEventDisableTiming));
         }
-    {
-        gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-        const void* iq = nullptr;
-        int rc = rd.view(first_sample, (uint64_t)nblocks * a->K * a->consumed, &iq);
-        if (rc != GSDR_OK) return rc;
-        rc = rd.acquire(a->stream);
-        if (rc != GSDR_OK) return rc;
-        rc = dispatch(a, 0, iq, nblocks, a->consumed, stamp0, a->d_res, a->stream, 0);
-        if (rc != GSDR_OK) return rc;
-        rc = rd.release(a->stream);
-        if (rc != GSDR_OK) return rc;
-    }
+    int rc = run_ring(a, ring, first_sample, nblocks, stamp0);
+    if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipMemcpyAsync(a->h_res[slot], a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result),
         hipMemcpyDeviceToHost, a->stream));
     GSDR_HIP(hipEventRecord(a->sub_done[slot], a->stream));
@@ -590,19 +545,20 @@ int gsdr_acq_run_dwell(gsdr_acq* a, const void* iq_host, uint32_t dwell, uint64_
     GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_dwell: set_local_codes first");
     GSDR_REQUIRE(dwell < a->conf.max_dwells, GSDR_E_ARG, "gsdr_acq_run_dwell: dwell %u outside [0,%u)", dwell,
         a->conf.max_dwells);
-    GSDR_REQUIRE(!a->st2.active, GSDR_E_STATE, "gsdr_acq_run_dwell: step two in progress");
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     if (!a->d_dgrid)
         GSDR_HIP(hipMalloc(&a->d_dgrid, (size_t)a->conf.max_prns * a->D * a->eff * sizeof(float)));
-    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * item_bytes(a->conf.item_type),
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 5, nullptr, 1, a->consumed, stamp, a->d_res, a->stream, dwell);
+    AcqOp op{AcqOp::Dwell};
+    op.dwell = dwell;
+    op.stamp0 = stamp;
+    op.res = a->d_res;
+    op.s = a->stream;
+    int rc = dispatch(a, view_of(a), op);
     if (rc != GSDR_OK) return rc;
-    GSDR_HIP(hipMemcpyAsync(out, a->d_res, (size_t)a->nprn * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost,
-        a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    return read_results(a, out, a->nprn);
 }
 
 int gsdr_acq_dump_spectra(gsdr_acq* a, const void* iq_host, float* spectra_host)
@@ -610,9 +566,9 @@ int gsdr_acq_dump_spectra(gsdr_acq* a, const void* iq_host, float* spectra_host)
     GSDR_REQUIRE(a && iq_host && spectra_host, GSDR_E_ARG, "gsdr_acq_dump_spectra: null argument");
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
-    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * item_bytes(a->conf.item_type),
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 2, nullptr, 1, 0, 0, nullptr, a->stream, 0);
+    int rc = dispatch(a, view_of(a), AcqOp{AcqOp::DumpSpectra});
     if (rc != GSDR_OK) return rc;
     // row d of block 0 wherever the layout keeps it (XMap: a window of a shared spectrum)
     for (uint32_t d = 0; d < a->D; ++d)
@@ -628,9 +584,11 @@ int gsdr_acq_dump_grid(gsdr_acq* a, const void* iq_host, uint32_t prn_slot, floa
     GSDR_REQUIRE(prn_slot < a->nprn, GSDR_E_ARG, "gsdr_acq_dump_grid: prn_slot %u >= nprn %u", prn_slot, a->nprn);
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
-    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * item_bytes(a->conf.item_type),
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
-    int rc = dispatch(a, 3, nullptr, 1, 0, 0, nullptr, a->stream, prn_slot);
+    AcqOp op{AcqOp::DumpGrid};
+    op.prn_slot = prn_slot;
+    int rc = dispatch(a, view_of(a), op);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipMemcpyAsync(grid_host, a->d_grid, (size_t)a->D * a->N * sizeof(float), hipMemcpyDeviceToHost,
         a->stream));
@@ -650,33 +608,21 @@ int gsdr_acq_dump_grid_step_two(gsdr_acq* a, const void* iq_host, uint32_t prn_s
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     const uint32_t nb = a->st2.nbins;
-    // update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), as gsdr_acq_run_step_two
-    const float half = (float)std::floor((double)nb / 2.0);
     std::vector<float> freqs(nb);
-    for (uint32_t d = 0; d < nb; ++d)
-        {
-            volatile float dop = ((float)d - half) * a->st2.step;
-            freqs[d] = doppler_center_hz + dop;
-        }
-    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * item_bytes(a->conf.item_type),
+    step_two_freqs(a, doppler_center_hz, freqs.data());
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
     GSDR_HIP(hipMemcpyAsync(a->st2.d_freq, freqs.data(), nb * sizeof(float), hipMemcpyHostToDevice, a->stream));
-    hipLaunchKernelGGL(acq_wipeoff_kernel, dim3(nb), dim3(256), 0, a->stream, a->st2.d_wipe, a->N,
-        (float)a->conf.fs_in, 0, 0, 0, 0, (const float*)a->st2.d_freq, a->wipe_mode);
-    GSDR_HIP(hipGetLastError());
-    // the grid dump on a one-PRN view with the narrow Doppler rows
-    const uint32_t D0 = a->D, P0 = a->nprn;
-    float2* const wipe0 = a->d_wipe;
-    float2* const code0 = a->d_code_fft;
-    a->D = nb;
-    a->nprn = 1;
-    a->d_wipe = a->st2.d_wipe;
-    a->d_code_fft = code0 + (size_t)prn_slot * a->N;
-    const int rc = dispatch(a, 3, nullptr, 1, 0, 0, nullptr, a->stream, 0);
-    a->D = D0;
-    a->nprn = P0;
-    a->d_wipe = wipe0;
-    a->d_code_fft = code0;
+    int rc = launch_wipeoff(a, a->st2.d_wipe, nb, a->st2.d_freq);
+    if (rc != GSDR_OK) return rc;
+    // the grid dump on a one-PRN view with the narrow Doppler rows (plain layout)
+    AcqView v = view_of(a);
+    v.D = nb;
+    v.nprn = 1;
+    v.wipe = a->st2.d_wipe;
+    v.code_fft = a->d_code_fft + (size_t)prn_slot * a->N;
+    v.xm = XMap{nb, 0u, a->N};
+    rc = dispatch(a, v, AcqOp{AcqOp::DumpGrid});
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipMemcpyAsync(grid_host, a->d_grid, (size_t)nb * a->N * sizeof(float), hipMemcpyDeviceToHost,
         a->stream));
@@ -730,53 +676,24 @@ int gsdr_acq_run_step_two(gsdr_acq* a, const void* iq_host, uint32_t nsel, const
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     const uint32_t nb = a->st2.nbins;
-    // update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), float arithmetic
-    const float half = (float)std::floor((double)nb / 2.0);
     std::vector<float> freqs((size_t)nsel * nb);
-    for (uint32_t i = 0; i < nsel; ++i)
-        for (uint32_t d = 0; d < nb; ++d)
-            {
-                volatile float dop = ((float)d - half) * a->st2.step;
-                freqs[(size_t)i * nb + d] = doppler_center_hz[i] + dop;
-            }
-    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->K * a->consumed * item_bytes(a->conf.item_type),
+    for (uint32_t i = 0; i < nsel; ++i) step_two_freqs(a, doppler_center_hz[i], freqs.data() + (size_t)i * nb);
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->K * a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
     GSDR_HIP(hipMemcpyAsync(a->st2.d_freq, freqs.data(), freqs.size() * sizeof(float), hipMemcpyHostToDevice,
         a->stream));
-    hipLaunchKernelGGL(acq_wipeoff_kernel, dim3(nsel * nb), dim3(256), 0, a->stream, a->st2.d_wipe, a->N,
-        (float)a->conf.fs_in, 0, 0, 0, 0, (const float*)a->st2.d_freq, a->wipe_mode);
-    GSDR_HIP(hipGetLastError());
+    int rc = launch_wipeoff(a, a->st2.d_wipe, nsel * nb, a->st2.d_freq);
     // one narrow grid per PRN (each has its own centre): the engine's launches on a
-    // one-PRN view of the handle
-    const uint32_t D0 = a->D, P0 = a->nprn;
-    float2* const wipe0 = a->d_wipe;
-    float2* const code0 = a->d_code_fft;
-    uint32_t* const prn0 = a->d_prn;
+    // one-PRN view with that PRN's rows, plain layout and step-two parameters
     const float thr = step_two_threshold(a);
-    int rc = GSDR_OK;
     for (uint32_t i = 0; i < nsel && rc == GSDR_OK; ++i)
         {
-            a->D = nb;
-            a->nprn = 1;
-            a->d_wipe = a->st2.d_wipe + (size_t)i * nb * a->N;
-            a->d_code_fft = code0 + (size_t)prn_slots[i] * a->N;
-            a->d_prn = prn0 + prn_slots[i];
-            a->st2.active = true;
-            a->st2.center = doppler_center_hz[i];
-            a->st2.ip = coarse_input_power[i];
-            a->st2.threshold = thr;
-            rc = dispatch(a, 0, a->d_iq, 1, a->consumed, stamp, a->d_res + i, a->stream, 0);
+            const AcqView v{nb, 1, a->st2.d_wipe + (size_t)i * nb * a->N, a->d_code_fft + (size_t)prn_slots[i] * a->N,
+                a->d_prn + prn_slots[i], XMap{nb, 0u, a->N}, true, doppler_center_hz[i], coarse_input_power[i], thr};
+            rc = run_blocks(a, v, a->d_iq, 1, a->consumed, stamp, a->d_res + i, a->stream);
         }
-    a->D = D0;
-    a->nprn = P0;
-    a->d_wipe = wipe0;
-    a->d_code_fft = code0;
-    a->d_prn = prn0;
-    a->st2.active = false;
     if (rc != GSDR_OK) return rc;
-    GSDR_HIP(hipMemcpyAsync(out, a->d_res, (size_t)nsel * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    return read_results(a, out, nsel);
 }
 
 int gsdr_acq_set_cu_mask(gsdr_acq* a, const uint32_t* mask, int n_words)

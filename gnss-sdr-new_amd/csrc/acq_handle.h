@@ -1,0 +1,196 @@
+// Host side shared by the acquisition translation units: the handle, the view a
+// launch runs on, the typed operation of the per-plan dispatch, and the host
+// helpers and launch functions each defined in one unit.
+#pragma once
+#include <mutex>
+#include <type_traits>
+#include <vector>
+
+#include "acq_kernels.h"
+
+// Runtime switches, read once per handle by read_acq_env (acq_common.hip, which
+// documents each of them).
+struct AcqEnv
+{
+    int wipe_mode{GSDR_WIPE_EXACT};
+    bool xshift{true}, four_generic{false}, split{true}, split_arg{true};
+    int qpw{0}, ppw{0};
+    int corr_variant{-1};  // -1: default_pk_variant(N)
+};
+
+// ====================================================================== handle
+struct gsdr_acq
+{
+    int device{0};
+    gsdr_acq_conf conf{};
+    AcqEnv env{};
+    uint32_t N{0}, D{0}, consumed{0}, lead{0};
+    uint32_t K{1};       // max_dwells
+    int wipe_mode{GSDR_WIPE_EXACT};  // carrier model of the Doppler grid (gsdr_acq_set_wipeoff)
+    gsdr_acq_impl::XMap xm{};  // forward-spectrum layout of the main Doppler grid (rebuild_wipeoffs)
+    uint32_t eff{0};     // effective FFT size (outputs [N - eff, N))
+    bool general{false}; // dwells > 1 or bit transition: the general kernels
+    gsdr_acq_result* d_resk{nullptr};  // per-dwell results (general path)
+    float* d_acc{nullptr};             // pooled |R|^2 accumulation rows (general path)
+    uint32_t* d_acc_slots{nullptr};
+    int acc_words{0};
+    float threshold{0.0f};
+    int nt{256};
+    int variant{0};           // FFT plan id (acq_plans.h)
+    int corr_variant{0};      // 0: the generic LDS kernels; >0: a PkVariants id (packed forward + correlate, acq_pk.hip)
+    int split{0};             // >0: the single-dwell split register four-step correlate (acq_split.hip)
+    int corr_stat{0};         // the variant's row statistic (1/2: argmax recomputed by acq_argmax_pk_kernel)
+    size_t corr_lds_bytes{0};
+    gsdr::fft::Plan plan{};
+    gsdr::fft::Plan4 plan4{};  // four-step plan (variants 20-27, N beyond one workgroup's LDS)
+    size_t lds_bytes{0};
+    hipStream_t stream{nullptr};
+    float2* d_tw{nullptr};
+    float2* d_wipe{nullptr};
+    float2* d_code_fft{nullptr};
+    float2* d_code_stage{nullptr};
+    uint32_t* d_prn{nullptr};
+    uint32_t nprn{0};
+    float2* d_X{nullptr};
+    gsdr_acq_impl::RowStat* d_stats{nullptr};
+    gsdr_acq_result* d_res{nullptr};
+    // gsdr_acq_submit_stream / gsdr_acq_collect: up to kSubs submissions in flight,
+    // each with its pinned results (max_blocks x max_prns), completion event and shape;
+    // a later submission's grid reuses d_res on the same stream, ordered after the
+    // earlier one's copy out of it
+    static constexpr int kSubs = 2;
+    gsdr_acq_result* h_res[kSubs]{};
+    hipEvent_t sub_done[kSubs]{};
+    uint32_t sub_blocks[kSubs]{}, sub_nprn[kSubs]{};
+    int sub_head{0}, sub_count{0};
+    void* d_iq{nullptr};
+    float* d_grid{nullptr};
+    float* d_rowbuf{nullptr};  // split path, peak ratio: the selected rows' |R|^2 (max_blocks x max_prns x N)
+    unsigned long long* d_keys{nullptr};  // split path: the selected rows' first-maximum keys (max_blocks x max_prns)
+    float* d_psum{nullptr};               // split path, CFAR: Parseval shares per sub-transform (max_blocks x max_prns x 4)
+    float2* d_fscratch{nullptr};  // split path: the two-launch forward's column-DFT rows (max_blocks x D x N)
+    float* d_dgrid{nullptr};     // gsdr_acq_run_dwell: the |R|^2 grid kept across calls (max_prns x D x eff)
+    float2* d_tw_sub{nullptr};   // four-step: W_N2 table
+    float2* d_scratch{nullptr};  // four-step: slot rows of N complex
+    uint32_t* d_slots{nullptr};  // four-step: slot occupancy bitmap
+    // stage profiling (gsdr_acq_set_profiling)
+    struct ProfRec
+    {
+        hipEvent_t a, b;
+        int stage;
+    };
+    bool profiling{false};
+    std::vector<ProfRec> prof_recs;
+    std::vector<hipEvent_t> prof_pool;
+    // make_two_steps (gsdr_acq_set_step_two / gsdr_acq_run_step_two)
+    struct StepTwo
+    {
+        uint32_t nbins{0};       // num_doppler_bins_step2
+        float step{0.0f};        // doppler_step2
+        float pfa2{0.0f};
+        float2* d_wipe{nullptr}; // max_prns x nbins rows of N
+        float* d_freq{nullptr};
+    } st2;
+    std::mutex mu;
+};
+
+namespace gsdr_acq_impl
+{
+
+// What a launch runs on: the Doppler rows, PRNs and spectrum layout in effect.
+// Built from the handle at the top of each ABI call (view_of); step two builds a
+// one-PRN view over its narrow rows instead of altering the handle.
+struct AcqView
+{
+    uint32_t D, nprn;
+    const float2* wipe;      // D wipe-off rows (xm.q of them with the spectrum reuse)
+    const float2* code_fft;  // nprn code spectra
+    const uint32_t* prn;     // their PRN ids
+    XMap xm;
+    // make_two_steps narrow grid (AcqParams::step_two ...)
+    bool step_two;
+    float center2, ip2, threshold2;
+};
+
+// The operation of a per-plan dispatch, with the arguments each kind reads.
+struct AcqOp
+{
+    enum Kind
+    {
+        Run,          // iq, nblocks, stride, stamp0, res, s
+        CodeFft,      // first_slot, nslots
+        DumpSpectra,  // (the block at d_iq)
+        DumpGrid,     // prn_slot
+        SetAttrs,
+        Dwell         // dwell, stamp0, res, s
+    } kind;
+    const void* iq{nullptr};
+    uint32_t nblocks{0};
+    uint64_t stride{0}, stamp0{0};
+    gsdr_acq_result* res{nullptr};
+    hipStream_t s{nullptr};
+    uint32_t first_slot{0}, nslots{0}, prn_slot{0}, dwell{0};
+};
+
+// Default packed correlate variant for an FFT size (0: none, the generic kernels).
+inline int default_pk_variant(uint32_t N)
+{
+    switch (N)
+        {
+        case 4000: return 70;
+        case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
+        case 8000: return 61;
+        case 2000: return 62;
+        default: return 0;
+        }
+}
+
+// f(std::integral_constant<int, GSDR_ITEM_*>) for a runtime item type.
+template <class F>
+auto with_item_type(int it, F&& f)
+{
+    if (it == GSDR_ITEM_GR_COMPLEX) return f(std::integral_constant<int, GSDR_ITEM_GR_COMPLEX>{});
+    if (it == GSDR_ITEM_CSHORT) return f(std::integral_constant<int, GSDR_ITEM_CSHORT>{});
+    return f(std::integral_constant<int, GSDR_ITEM_IBYTE>{});
+}
+constexpr int kItemTypes[] = {GSDR_ITEM_GR_COMPLEX, GSDR_ITEM_CSHORT, GSDR_ITEM_IBYTE};
+
+inline int set_max_lds(const void* kernel, size_t bytes)
+{
+    GSDR_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return GSDR_OK;
+}
+
+// acq_common.hip
+AcqEnv read_acq_env();
+AcqView view_of(const gsdr_acq* a);
+AcqParams params_of(const gsdr_acq* a, const AcqView& v);
+int rebuild_wipeoffs(gsdr_acq* a);
+void compute_threshold(gsdr_acq* a);
+float step_two_threshold(const gsdr_acq* a);
+// the kernels that are no templates: rows of Doppler wipe-offs (freqs, or the main
+// grid of the handle's configuration when null), the grid maximum and statistic per
+// (block, PRN) or (dwells) per (block, PRN, dwell), the dwell decision, the second peak
+// of gsdr_acq_run_dwell's accumulated grid
+int launch_wipeoff(gsdr_acq* a, float2* wipe, uint32_t rows, const float* freqs);
+int launch_reduce(gsdr_acq* a, const AcqParams& ap, bool dwells, uint32_t nblocks, gsdr_acq_result* res,
+    const uint32_t* prn, uint64_t stamp0, uint64_t stride, hipStream_t s);
+int launch_decide(gsdr_acq* a, uint32_t n, gsdr_acq_result* res, hipStream_t s);
+int launch_grid_second_peak(gsdr_acq* a, const AcqParams& ap, gsdr_acq_result* res, hipStream_t s);
+
+// acq_pk.hip
+int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStream_t s);
+int launch_argmax_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, gsdr_acq_result* res, hipStream_t s);
+int launch_forward_pk(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, hipStream_t s);
+int setup_corr_variant(gsdr_acq* a, int id);
+// acq_split.hip
+int setup_split(gsdr_acq* a);
+int launch_split(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStream_t s);
+int launch_split_argmax(gsdr_acq* a, const AcqView& v, uint32_t nblocks, gsdr_acq_result* res, hipStream_t s);
+// acq_v_static.hip, acq_v_runtime.hip, acq_v_four.hip: the plans of acq_plans.h, one
+// group per unit so the heavy instantiations compile in parallel
+int dispatch_static(gsdr_acq* a, const AcqView& v, const AcqOp& op);
+int dispatch_runtime(gsdr_acq* a, const AcqView& v, const AcqOp& op);
+int dispatch_four(gsdr_acq* a, const AcqView& v, const AcqOp& op);
+
+}  // namespace gsdr_acq_impl

@@ -1,12 +1,16 @@
-// Packed-f32 correlate-kernel variants for N = 4000 (the C2 bench configuration):
-// launch and one-time setup, selected by gsdr_acq::corr_variant.
-#include <cstdlib>
-#include "acq_impl.h"
+// Packed-f32 forward / correlate / argmax variants, one per compile-time FFT size
+// (N = 2000, 4000, 8000, 16000): launch and one-time setup, selected by
+// gsdr_acq::corr_variant.
+#include "acq_handle.h"
+#include "acq_plans.h"
+#include "acq_split_kernels.h"
 
 namespace gsdr_acq_impl
 {
+namespace
+{
 
-// The variant whose correlate kernel is not acq_correlate_pk_kernel (its forward
+// The variants whose correlate kernel is not acq_correlate_pk_kernel (their forward
 // and argmax passes use the variant's PkPlan): 93 = N 16000 on the register
 // four-step 16 x (10 x 10 x 10), 512 lanes, 8 rows per LDS round, each XCD's
 // rows walked in groups of 16 PRNs.
@@ -15,144 +19,124 @@ using RegPlan93 = RegFourStep<16, 512, 8, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // inside a row transform)
 using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 10>;
 
-template <class RP>
-int launch_reg(gsdr_acq* a, uint32_t nblocks, hipStream_t s)
+// A variant (default_pk_variant; GSDR_ACQ_CORR_VARIANT selects one for tests): id,
+// plan, PRNs per workgroup, waves-per-EU hint, row statistic (1 max + sum with the
+// argmax recomputed for the selected row, 2 max only with the CFAR row sum by
+// Parseval -- see acq_correlate_pk_kernel) and, for 93 / 94, the register four-step
+// the correlate runs on instead (acq_correlate_reg_kernel, N = 16000, PRN-group-major
+// XCD walk).  The alternatives measured in
+// rounds 1-4 and removed: other radix orders, per-stage twiddle
+// tables (-23 %) and LDS root copies (-2.5 %), padded layouts, late or dropped
+// barriers, 5 waves per SIMD (with spills -19 %; without, the first-stage products
+// in two halves, -2 %), 3 / 2 workgroups per CU (-8 % / -26 %), per-wave atomic row
+// maxima (-2 %), multi-transform workgroups: variant 70 at 104 VGPRs runs 4
+// workgroups (16 waves) per CU, where the CU's issue, not latency, bounds it.
+template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void>
+struct PkVariant
 {
-    hipLaunchKernelGGL((acq_correlate_reg_kernel<RP>), dim3(nblocks * a->D * a->nprn), dim3(RP::NT), RP::lds_bytes(),
-        s, a->d_X, a->d_code_fft, a->d_stats, a->d_tw, a->D, a->nprn, nblocks, a->xm);
-    return GSDR_OK;
+    static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST;
+    using type = MP;
+    using Reg = REG;
+};
+using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1>,
+    PkVariant<62, PkPlan<256, true, 20, 10, 10>, 1, 1, 1>,
+    PkVariant<93, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan93>,
+    PkVariant<94, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan94>,
+    PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>>;
+
+// f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
+// internal error in a launch: setup accepted the handle's id).
+template <class F>
+int with_pk_variant(int id, F&& f, int unknown = GSDR_E_STATE)
+{
+    int rc = unknown;
+    const bool found = find_plan(PkVariants{}, [&](auto e) {
+        if (decltype(e)::id != id) return false;
+        rc = f(e);
+        return true;
+    });
+    if (!found && unknown != GSDR_OK) gsdr::set_error("internal: bad correlate variant %d", id);
+    return rc;
 }
 
-template <class RP>
-int setup_reg()
+}  // namespace
+
+int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStream_t s)
 {
-    GSDR_HIP(hipFuncSetAttribute((const void*)acq_correlate_reg_kernel<RP>, hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)RP::lds_bytes()));
-    return GSDR_OK;
+    return with_pk_variant(a->corr_variant, [&](auto e) {
+        using V = decltype(e);
+        using M = typename V::type;
+        if constexpr (!std::is_void<typename V::Reg>::value)
+            {
+                using RP = typename V::Reg;
+                hipLaunchKernelGGL((acq_correlate_reg_kernel<RP>), dim3(nblocks * v.D * v.nprn), dim3(RP::NT),
+                    RP::lds_bytes(), s, a->d_X, v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks, v.xm);
+            }
+        else
+            {
+                const uint32_t groups = (v.nprn + pg_count(V::PG) - 1) / pg_count(V::PG);
+                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT>), dim3(nblocks * v.D * groups),
+                    dim3(M::NT), a->corr_lds_bytes, s, a->d_X, v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
+                    v.xm);
+            }
+        return GSDR_OK;
+    });
 }
 
-int launch_corr_variant(gsdr_acq* a, uint32_t nblocks, hipStream_t s)
+// The variants' first-maximum pass over the selected rows.
+int launch_argmax_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, gsdr_acq_result* res, hipStream_t s)
 {
-    switch (a->corr_variant)
-        {
-        case 93: return launch_reg<RegPlan93>(a, nblocks, s);
-        case 94: return launch_reg<RegPlan94>(a, nblocks, s);
-        default: break;
-        }
-#define GSDR_PK_CASE(ID, MP, PG, WPE, ST)                                                                       \
-    case ID:                                                                                                    \
-        {                                                                                                       \
-            using M = GSDR_UNPAREN MP;                                                                          \
-            const uint32_t groups = (a->nprn + pg_count(PG) - 1) / pg_count(PG);                                                  \
-            if (ST == 3)                                                                                        \
-                GSDR_HIP(hipMemsetAsync(a->d_stats, 0, (size_t)nblocks * a->nprn * a->D * sizeof(RowStat), s)); \
-            hipLaunchKernelGGL((acq_correlate_pk_kernel<M, PG, WPE, ST>), dim3(nblocks * a->D * groups),         \
-                dim3(M::NT), a->corr_lds_bytes, s, a->d_X, a->d_code_fft, a->d_stats, a->d_tw, a->D, a->nprn,   \
-                nblocks, a->xm);                                                                                \
-            return GSDR_OK;                                                                                     \
-        }
-#define GSDR_UNPAREN(...) __VA_ARGS__
-    switch (a->corr_variant)
-        {
-            GSDR_PK_VARIANTS(GSDR_PK_CASE)
-        default: gsdr::set_error("internal: bad correlate variant %d", a->corr_variant); return GSDR_E_STATE;
-        }
-#undef GSDR_PK_CASE
-#undef GSDR_UNPAREN
-}
-
-// The STAT-1 variants' first-maximum pass over the selected rows.
-int launch_argmax_variant(gsdr_acq* a, uint32_t nblocks, gsdr_acq_result* res, hipStream_t s)
-{
-#define GSDR_PKA_CASE(ID, MP, PG, WPE, ST)                                                                      \
-    case ID:                                                                                                    \
-        {                                                                                                       \
-            using M = GSDR_UNPAREN MP;                                                                          \
-            hipLaunchKernelGGL((acq_argmax_pk_kernel<M, ST>), dim3(nblocks * a->nprn), dim3(M::NT),             \
-                a->corr_lds_bytes, s, a->d_X, a->d_code_fft, res, a->d_tw, a->D, a->nprn,                       \
-                a->conf.samples_per_code, params_of(a));                                                        \
-            GSDR_HIP(hipGetLastError());                                                                        \
-            return GSDR_OK;                                                                                     \
-        }
-#define GSDR_UNPAREN(...) __VA_ARGS__
-    switch (a->corr_variant)
-        {
-            GSDR_PK_VARIANTS(GSDR_PKA_CASE)
-        default: gsdr::set_error("internal: bad argmax variant %d", a->corr_variant); return GSDR_E_STATE;
-        }
-#undef GSDR_PKA_CASE
-#undef GSDR_UNPAREN
+    return with_pk_variant(a->corr_variant, [&](auto e) {
+        using V = decltype(e);
+        using M = typename V::type;
+        hipLaunchKernelGGL((acq_argmax_pk_kernel<M, V::STAT>), dim3(nblocks * v.nprn), dim3(M::NT), a->corr_lds_bytes,
+            s, a->d_X, v.code_fft, res, a->d_tw, v.D, v.nprn, a->conf.samples_per_code, params_of(a, v));
+        GSDR_HIP(hipGetLastError());
+        return GSDR_OK;
+    });
 }
 
 // Forward spectra on the packed plan of the selected variant.
-int launch_forward_pk(gsdr_acq* a, const void* iq, int item_type, uint32_t nblocks, uint64_t stride, hipStream_t s)
+int launch_forward_pk(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, hipStream_t s)
 {
-#define GSDR_PKF_CASE(ID, MP, PG, WPE, ST)                                                                          \
-    case ID:                                                                                                    \
-        {                                                                                                       \
-            using M = GSDR_UNPAREN MP;                                                                          \
-            if (item_type == GSDR_ITEM_GR_COMPLEX)                                                              \
-                hipLaunchKernelGGL((acq_forward_pk_kernel<M, GSDR_ITEM_GR_COMPLEX>), dim3(nblocks, a->xm.q),       \
-                    dim3(M::NT), M::lds_bytes(), s, iq, stride, a->d_wipe, a->d_X, a->d_tw, a->consumed, a->xm); \
-            else if (item_type == GSDR_ITEM_CSHORT)                                                             \
-                hipLaunchKernelGGL((acq_forward_pk_kernel<M, GSDR_ITEM_CSHORT>), dim3(nblocks, a->xm.q),           \
-                    dim3(M::NT), M::lds_bytes(), s, iq, stride, a->d_wipe, a->d_X, a->d_tw, a->consumed, a->xm); \
-            else                                                                                                \
-                hipLaunchKernelGGL((acq_forward_pk_kernel<M, GSDR_ITEM_IBYTE>), dim3(nblocks, a->xm.q),            \
-                    dim3(M::NT), M::lds_bytes(), s, iq, stride, a->d_wipe, a->d_X, a->d_tw, a->consumed, a->xm); \
-            GSDR_HIP(hipGetLastError());                                                                        \
-            return GSDR_OK;                                                                                     \
-        }
-#define GSDR_UNPAREN(...) __VA_ARGS__
-    switch (a->corr_variant)
-        {
-            GSDR_PK_VARIANTS(GSDR_PKF_CASE)
-        default: gsdr::set_error("internal: bad forward variant %d", a->corr_variant); return GSDR_E_STATE;
-        }
-#undef GSDR_PKF_CASE
-#undef GSDR_UNPAREN
+    return with_pk_variant(a->corr_variant, [&](auto e) {
+        using M = typename decltype(e)::type;
+        with_item_type(a->conf.item_type, [&](auto t) {
+            hipLaunchKernelGGL((acq_forward_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q), dim3(M::NT),
+                M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->consumed, v.xm);
+        });
+        GSDR_HIP(hipGetLastError());
+        return GSDR_OK;
+    });
 }
 
-// Select and configure a correlate variant (N must be 4000).
-int setup_corr_variant(gsdr_acq* a, int v)
+// Select and configure a correlate variant for the handle's N; an id not in the
+// list leaves the generic kernels.
+int setup_corr_variant(gsdr_acq* a, int id)
 {
-
-#define GSDR_PK_SETUP(ID, MP, PG, WPE, ST)                                                                      \
-    case ID:                                                                                                    \
-        {                                                                                                       \
-            using M = GSDR_UNPAREN MP;                                                                          \
-            a->corr_lds_bytes = M::lds_bytes() + (size_t)2 * (M::NT / 64) * sizeof(RowStat);                   \
-            GSDR_HIP(hipFuncSetAttribute((const void*)acq_correlate_pk_kernel<M, PG, WPE, ST>,                  \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->corr_lds_bytes));                           \
-            GSDR_HIP(hipFuncSetAttribute((const void*)acq_argmax_pk_kernel<M, ST>,                              \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->corr_lds_bytes));                           \
-            if (M::N != (int)a->N)                                                                              \
-                {                                                                                               \
-                    gsdr::set_error("correlate variant %d is for N = %d, not %u", ID, M::N, a->N);            \
-                    return GSDR_E_UNSUPPORTED;                                                                  \
-                }                                                                                               \
-            GSDR_HIP(hipFuncSetAttribute((const void*)acq_forward_pk_kernel<M, GSDR_ITEM_GR_COMPLEX>,          \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)M::lds_bytes()));                              \
-            GSDR_HIP(hipFuncSetAttribute((const void*)acq_forward_pk_kernel<M, GSDR_ITEM_CSHORT>,              \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)M::lds_bytes()));                              \
-            GSDR_HIP(hipFuncSetAttribute((const void*)acq_forward_pk_kernel<M, GSDR_ITEM_IBYTE>,               \
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)M::lds_bytes()));                              \
-            if (ID == 93 && setup_reg<RegPlan93>() != GSDR_OK) return GSDR_E_DEVICE;                           \
-            if (ID == 94 && setup_reg<RegPlan94>() != GSDR_OK) return GSDR_E_DEVICE;                           \
-            a->corr_variant = ID;                                                                               \
-            a->corr_stat = ST;                                                                                  \
-            return GSDR_OK;                                                                                     \
-        }
-#define GSDR_UNPAREN(...) __VA_ARGS__
-    switch (v)
-        {
-            GSDR_PK_VARIANTS(GSDR_PK_SETUP)
-        default: a->corr_variant = 0; return GSDR_OK;
-        }
-#undef GSDR_PK_SETUP
-#undef GSDR_UNPAREN
+    a->corr_variant = 0;
+    return with_pk_variant(id, [&](auto e) {
+        using V = decltype(e);
+        using M = typename V::type;
+        if (M::N != (int)a->N)
+            {
+                gsdr::set_error("correlate variant %d is for N = %d, not %u", V::id, M::N, a->N);
+                return GSDR_E_UNSUPPORTED;
+            }
+        a->corr_lds_bytes = M::lds_bytes() + (size_t)2 * (M::NT / 64) * sizeof(RowStat);
+        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT>, a->corr_lds_bytes);
+        rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT>, a->corr_lds_bytes);
+        for (int it : kItemTypes)
+            rc |= with_item_type(it, [&](auto t) {
+                return set_max_lds((const void*)acq_forward_pk_kernel<M, decltype(t)::value>, M::lds_bytes());
+            });
+        if constexpr (!std::is_void<typename V::Reg>::value)
+            rc |= set_max_lds((const void*)acq_correlate_reg_kernel<typename V::Reg>, V::Reg::lds_bytes());
+        if (rc != GSDR_OK) return GSDR_E_DEVICE;
+        a->corr_variant = V::id;
+        a->corr_stat = V::STAT;
+        return GSDR_OK;
+    }, GSDR_OK);
 }
-
-// The plan object a plan type's kernels take (LDS plan or four-step plan).
 
 }  // namespace gsdr_acq_impl

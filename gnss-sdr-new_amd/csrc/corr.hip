@@ -489,8 +489,6 @@ struct gsdr_corr
 namespace
 {
 
-size_t item_bytes(int it) { return it == GSDR_ITEM_CSHORT ? 4 : (it == GSDR_ITEM_IBYTE ? 2 : 8); }
-
 // The reference's host-side phasors, bit for bit (std::cos/std::sin/std::exp on
 // float, cpu_multicorrelator_real_codes.cc:114-123), reduced to their angles.
 JobAux host_model(const gsdr_corr_job& j)
@@ -764,7 +762,7 @@ int gsdr_corr_run(gsdr_corr* c, int ch, const void* sig_in_host, int item_type, 
     {
         std::lock_guard<std::mutex> lk(c->mu);
         gsdr::DeviceGuard g(c->device);
-        GSDR_HIP(hipMemcpyAsync(c->d_iq, sig_in_host, (size_t)n * item_bytes(item_type), hipMemcpyHostToDevice,
+        GSDR_HIP(hipMemcpyAsync(c->d_iq, sig_in_host, (size_t)n * gsdr::item_bytes(item_type), hipMemcpyHostToDevice,
             c->stream));
     }
     int rc = gsdr_corr_run_batch(c, &jb, 1, c->d_iq, item_type, n, (float*)c->d_out, c->stream);

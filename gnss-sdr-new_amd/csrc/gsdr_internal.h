@@ -38,6 +38,9 @@ void set_error(const char* fmt, ...);
         }                                            \
     while (0)
 
+// Bytes of one complex sample of a GSDR_ITEM_* type.
+inline size_t item_bytes(int it) { return it == GSDR_ITEM_CSHORT ? 4 : (it == GSDR_ITEM_IBYTE ? 2 : 8); }
+
 // RAII device switch: the ABI is called from arbitrary host threads.
 struct DeviceGuard
 {

@@ -251,11 +251,6 @@ int StreamWriter::commit()
 }
 }  // namespace gsdr
 
-namespace
-{
-size_t bytes_of(int it) { return it == GSDR_ITEM_CSHORT ? 4 : (it == GSDR_ITEM_IBYTE ? 2 : 8); }
-}  // namespace
-
 extern "C" {
 
 int gsdr_stream_create(int device, int item_type, uint64_t capacity_items, uint64_t max_window_items, gsdr_stream** out)
@@ -274,7 +269,7 @@ int gsdr_stream_create(int device, int item_type, uint64_t capacity_items, uint6
     GSDR_REQUIRE(s, GSDR_E_ALLOC, "gsdr_stream_create: out of host memory");
     s->device = device;
     s->item_type = item_type;
-    s->item_bytes = bytes_of(item_type);
+    s->item_bytes = gsdr::item_bytes(item_type);
     s->cap = capacity_items;
     s->window = max_window_items;
     hipError_t e = hipMalloc(&s->d_ring, (size_t)(s->cap + s->window) * s->item_bytes);

@@ -2199,8 +2199,6 @@ struct gsdr_trk
 namespace
 {
 
-size_t trk_item_bytes(int it) { return it == GSDR_ITEM_CSHORT ? 4 : (it == GSDR_ITEM_IBYTE ? 2 : 8); }
-
 // constructor (dll_pll_veml_tracking.cc:85-560) for one channel slot, GPS L1 C/A
 // Tracking_FLL_PLL_filter::set_params (tracking_FLL_PLL_filter.cc:23-58)
 void cf_set_params(CfConst& p, float fll_bw, float pll_bw, int order)
@@ -2379,7 +2377,6 @@ constexpr size_t kStaticLdsMargin = 4 * 1024;  // the kernel's static __shared__
 // a tail of up to kTrkThreads samples) + 16 alignment bytes rounded up to whole
 // glds rows; chunk a multiple of kWinCore.  chunk = 0: no room (the
 // calls then read HBM directly).
-int item_size(int item_type) { return item_type == GSDR_ITEM_GR_COMPLEX ? 8 : (item_type == GSDR_ITEM_CSHORT ? 4 : 2); }
 int stream_buffer_bytes(int chunk, int isz) { return (((chunk + kHalo) * isz + 16) / kStreamRow + 2) * kStreamRow; }
 void stream_plan(size_t lds_bytes, int code_pad, int data_pad, int isz, int& chunk, int& sbuf)
 {
@@ -2442,7 +2439,7 @@ int launch(gsdr_trk* k, const void* iq, uint64_t iq_first, uint64_t iq_items, ui
         }
     const dim3 grid(k->conf.max_channels);
     int chunk = 0, sbuf = 0;
-    stream_plan(k->lds_bytes, k->code_pad, k->data_pad, item_size(k->conf.item_type), chunk, sbuf);
+    stream_plan(k->lds_bytes, k->code_pad, k->data_pad, (int)gsdr::item_bytes(k->conf.item_type), chunk, sbuf);
     if (k->conf.item_type == GSDR_ITEM_GR_COMPLEX)
         hipLaunchKernelGGL((trk_kernel<GSDR_ITEM_GR_COMPLEX>), grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
             (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out,
@@ -2978,7 +2975,7 @@ int gsdr_trk_run(gsdr_trk* k, const void* iq_host, uint64_t iq_first_sample, uin
     GSDR_REQUIRE(k && iq_host && out_host && n_out_host, GSDR_E_ARG, "gsdr_trk_run: null argument");
     std::lock_guard<std::mutex> lk(k->mu);
     gsdr::DeviceGuard g(k->device);
-    const size_t bytes = (size_t)iq_items * trk_item_bytes(k->conf.item_type);
+    const size_t bytes = (size_t)iq_items * gsdr::item_bytes(k->conf.item_type);
     if (iq_items > k->iq_cap)
         {
             if (k->d_iq) GSDR_HIP(hipFree(k->d_iq));

@@ -187,7 +187,7 @@ def test_bad_configuration_errors():
     assert e.value.code == gsdr.GSDR_E_STATE
 
 
-# Packed correlate variants (acq_impl.h GSDR_PK_VARIANTS): id -> sample rate of its
+# Packed correlate variants (acq_pk.hip PkVariants): id -> sample rate of its
 # FFT size.  Row statistic 1 (max + sum, argmax recomputed) and 2 (max only, the CFAR
 # row sum by Parseval in acq_argmax_pk_kernel) must both match the oracle.
 PK_VARIANTS = [(70, 4000000), (93, 16000000), (94, 16000000), (61, 8000000), (62, 2000000)]

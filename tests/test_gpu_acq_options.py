@@ -9,8 +9,11 @@ through gsdr_acq_get_split:
   GSDR_ACQ_QPW=1  100000 = 4 x 25000: one sub-transform per workgroup (split id 4; the
                   default, two per workgroup, is id 24)
   GSDR_ACQ_SPLIT=0  100000 on the packed four-step's general kernels (no split)
+  GSDR_ACQ_SPLIT_ARG=0  25000: the split path's selected rows recomputed on the packed
+                  four-step plan instead of on the split plan
 
-GSDR_ACQ_SPLIT_ARG is read once per process into a static and cannot be toggled here.
+Every switch is read when the handle is created and kept in it, GSDR_ACQ_SPLIT_ARG
+included, so handles created under different settings coexist in one process.
 """
 import pytest
 
@@ -67,6 +70,35 @@ def test_ppw2_active_count_changes(monkeypatch, pfa):
         check_records(res, acq, case, pfa)
         assert res.tobytes() == ref.tobytes(), nprn
     acq.close()
+
+
+@pytest.mark.parametrize("pfa", PFAS)
+def test_split_arg_off_25000(monkeypatch, pfa):
+    """GSDR_ACQ_SPLIT_ARG=0: the grid maximum's row recomputed on the packed four-step
+    (variant 27) for the first-maximum index, peak and CFAR power / second peak.  A
+    handle created afterwards without the switch, in the same process, is back on the
+    split plan's own pass: both pass the oracle checks and agree on every decision,
+    but their peaks are not bit-identical -- 25000 = 25 x (10 x 10 x 10) and 5 x (25 x
+    20 x 10) round differently (the oracle comparison in test_gpu_acq_sizes puts either
+    engine ~2e-7 from fp64, not at it), which is how the test tells the two paths apart."""
+    case = size_case(25000)
+    monkeypatch.setenv("GSDR_ACQ_PPW", "1")
+    monkeypatch.setenv("GSDR_ACQ_SPLIT_ARG", "0")
+    off = make_acq(case, pfa)
+    assert off.plan["split"] == 1 and off.plan["variant"] == 27, off.plan
+    res_off = check_size(off, case, pfa, "split_arg0")
+    monkeypatch.delenv("GSDR_ACQ_SPLIT_ARG")
+    dflt = make_acq(case, pfa)
+    assert dflt.plan["split"] == 1 and dflt.plan["variant"] == 27, dflt.plan
+    res_dflt = check_size(dflt, case, pfa, "split_arg_default")
+    for f in ("prn", "doppler_index", "code_phase", "doppler_hz", "positive"):
+        assert (res_off[f][:case.nvis] == res_dflt[f][:case.nvis]).all(), f
+    print("split_arg peaks off/default:", res_off["peak"], res_dflt["peak"])
+    assert res_off["peak"].tobytes() != res_dflt["peak"].tobytes()
+    # the first handle is still on its own path
+    assert off.run(case.x)[0].tobytes() == res_off.tobytes()
+    off.close()
+    dflt.close()
 
 
 @pytest.mark.parametrize("pfa", PFAS)

@@ -89,6 +89,40 @@ def test_two_steps_even_bins_and_fractional_step():
     _check(*out, fs, N, 0.01, 4, 62.5, 0.0)
 
 
+def test_step_two_leaves_the_handle_alone():
+    """run -> run_step_two -> run on one handle (N = 4000): the narrow grids run on a
+    view of their own, so the second run repeats the first byte for byte (all of the
+    handle's active PRNs filled in) and the Doppler bin count and spectrum reuse read
+    back as before."""
+    import ctypes
+
+    fs, N, nbins2, step2 = 4000000, 4000, 5, 100.0
+    sats = synth.random_constellation(6, seed_offset=11, cn0_dbhz=48.0)
+    x = synth.gps_l1_iq(fs, 2 * N, sats, seed_offset=11)
+    prns = np.array([s.prn for s in sats])
+    acq = gsdr.Acquisition(fs, N, 10000, 500, pfa=0.01, max_prns=len(prns))
+    acq.set_local_codes(np.stack([synth.gps_ca_sampled(int(p), fs, N) for p in prns]), prns)
+    acq.set_step_two(nbins2, step2)
+
+    def dims():
+        D, n = ctypes.c_uint32(), ctypes.c_uint32()
+        assert gsdr.load().gsdr_acq_get_dims(acq._h, ctypes.byref(D), ctypes.byref(n)) == 0
+        return D.value, n.value
+
+    dims0, reuse0 = dims(), acq.spectrum_reuse
+    assert dims0 == (acq.num_doppler_bins, N) and dims0[0] != nbins2
+    first = acq.run(x[:N])[0]
+    sel = np.nonzero(first["positive"])[0]
+    assert len(sel) >= 2, first
+    fine = acq.run_step_two(x[N:], sel, first["doppler_hz"][sel].astype(np.float32), first["input_power"][sel], stamp=N)
+    assert (fine["prn"] == prns[sel]).all()
+    second = acq.run(x[:N])[0]
+    assert (second["prn"] == prns).all()  # every active PRN's record written: the count is unchanged
+    assert second.tobytes() == first.tobytes()
+    assert dims() == dims0 and acq.spectrum_reuse == reuse0
+    acq.close()
+
+
 def test_two_steps_argument_errors():
     fs, N = 4000000, 4000
     acq = gsdr.Acquisition(fs, N, 5000, 500, pfa=0.01, max_prns=2)

@@ -1,5 +1,5 @@
 """The acquisition grid's carrier wipe-off models and the forward-spectrum reuse
-(include/gsdr.h gsdr_acq_set_wipeoff / gsdr_acq_get_spectrum_reuse, acq_impl.h XMap),
+(include/gsdr.h gsdr_acq_set_wipeoff / gsdr_acq_get_spectrum_reuse, acq_kernels.h XMap),
 through the C ABI.
 
 GNSS-SDR computes each Doppler row's carrier with volk_gnsssdr_s32f_sincos_32fc
