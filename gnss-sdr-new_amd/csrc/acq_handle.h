@@ -137,7 +137,7 @@ inline int default_pk_variant(uint32_t N)
 {
     switch (N)
         {
-        case 4000: return 70;
+        case 4000: return 97;  // X resident for 16 PRNs, code rows by LDS DMA: +5 % over 70
         case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
         case 8000: return 61;
         case 2000: return 62;

@@ -379,19 +379,59 @@ __global__ void __launch_bounds__(PT::NT) acq_correlate_kernel(const float2* __r
 //         summing its 4000 outputs: sum_n |R[n]|^2 = N sum_k |Y[k]|^2 for the
 //         unnormalised transform of Y = conj(X) C.
 //
-// PG < 0: groups of -PG PRNs without the next-code prefetch (the code values are
-// loaded by the first stage itself) -- for plans whose registers cannot hold
-// both first-stage operand sets through a transform (N = 16000 on 1024 lanes).
-constexpr int pg_count(int pg) { return pg < 0 ? -pg : pg; }
+// Where a transform's code-spectrum values come from (CS):
+//   kCodeVgpr    the next PRN's values are fetched into VGPRs by the hook while the
+//                current transform runs (both first-stage operand sets stay live
+//                through a transform: PG = 1, or plans with registers to spare);
+//   kCodeDirect  loaded by the first stage itself, X resident -- for plans whose
+//                registers cannot hold both operand sets (N = 16000 on 1024 lanes);
+//                the code-row latency is exposed on every transform;
+//   kCodeLds     X resident (but for its last XT values, see XT in the kernel), the
+//                code row staged through the FFT buffer: once the
+//                last stage has read its inputs and passed its barrier the buffer
+//                is dead until the next transform's first stage writes it, so each
+//                wave copies its share of code row q + 1 into it there with
+//                buffer_load ... lds (dwordx4, no VGPRs; row element i at byte 8 i)
+//                and the copy lands under the last stage's butterflies and the row
+//                maximum.  The wave waits for its own copies before the statistics
+//                barrier, which so also publishes the row; the next first stage
+//                reads its 25 code values from LDS (consecutive lanes, conflict
+//                free) and a barrier before its writes (pre() of fft_pk.h) keeps
+//                any wave from overwriting values another has yet to read: 6
+//                barriers per transform instead of 5, +2 N c2 of LDS traffic.  The
+//                copies move whole 1 KiB pieces per wave, so the buffer is rounded
+//                up to NW KiB (pk_fft_bytes) and the statistics scratch follows it.
+//                Same operands, product form and order as the other two: the row
+//                maxima are bit-identical.
+enum CodeSrc
+{
+    kCodeVgpr = 0,
+    kCodeDirect = 1,
+    kCodeLds = 2
+};
 
-template <class MP, int PG_, int WPE, int STAT>
+// bytes of the FFT buffer in front of the kernel's statistics scratch
+template <class MP, int CS>
+constexpr size_t pk_fft_bytes()
+{
+    constexpr size_t piece = (size_t)(MP::NT / 64) * 1024;
+    return CS == kCodeLds ? (MP::lds_bytes() + piece - 1) / piece * piece : MP::lds_bytes();
+}
+
+template <class MP, int PG, int WPE, int STAT, int CS>
 __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE))) acq_correlate_pk_kernel(const float2* __restrict__ X,
     const float2* __restrict__ code_fft, RowStat* __restrict__ stats, const float2* __restrict__ tw, uint32_t D,
     uint32_t P, uint32_t nblocks, XMap xm)
 {
-    static_assert(PG_ != 0, "PRN group");
-    constexpr int PG = pg_count(PG_);
-    constexpr bool PREFETCH = PG_ > 0;
+    static_assert(PG > 0, "PRN group");
+    static_assert(CS == kCodeVgpr || CS == kCodeDirect || CS == kCodeLds, "code source");
+    constexpr bool PREFETCH = CS == kCodeVgpr;
+    constexpr bool STAGED = CS == kCodeLds;
+    // kCodeLds: the last XT of the lane's R1 X values are not resident either: all
+    // R1 of them beside the last stage's two passes and the first radix's working
+    // set do not fit the 128 VGPRs of four workgroups per CU (the compiler spilled
+    // 10), so the first stage loads those itself, as kCodeDirect loads the code.
+    constexpr int XT = STAGED ? (MP::R1 + 4) / 5 : 0;
     static_assert(STAT == 1 || STAT == 2, "row statistic 1 (max + sum) or 2 (max)");
     using gsdr::pk::c2;
     constexpr int NT = MP::NT;
@@ -400,7 +440,7 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     constexpr uint32_t N = MP::N;
     extern __shared__ float2 lds_raw[];
     c2* lds = reinterpret_cast<c2*>(lds_raw);
-    RowStat* scratch = reinterpret_cast<RowStat*>(lds_raw + MP::lds_bytes() / sizeof(float2));
+    RowStat* scratch = reinterpret_cast<RowStat*>(lds_raw + pk_fft_bytes<MP, CS>() / sizeof(float2));
     const uint32_t G = (P + PG - 1) / PG;
     const uint32_t nrows = nblocks * D;
     const uint32_t id = blockIdx.x;
@@ -445,20 +485,62 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                 {
                     const int jj = min(j, NB1 - 1);
 #pragma unroll
-                    for (int r = 0; r < R1; ++r)
+                    for (int r = 0; r < R1 - XT; ++r)
                         {
                             xr[bb][r] = bload(xrs, jj * 8, r * NB1 * 8);
                             if constexpr (PREFETCH) cr[bb][r] = bload(crs, jj * 8, r * NB1 * 8);
                         }
                 }
         }
+    // kCodeLds: this wave's 1 KiB pieces of code row qn into the FFT buffer (lane
+    // part in voffset, the row and the piece as the uniform scalar offset); the
+    // last piece may run past the row's end -- into the next row, or past the
+    // descriptor's (zeros) -- and lands in the buffer's padding, which no lane reads
+    auto stage_code = [&](int qn) {
+        constexpr int PIECE = NW * 1024;
+        constexpr int PIECES = (int)(pk_fft_bytes<MP, CS>() / PIECE);
+        // (uniform: the destination goes to M0)
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        char* dst = reinterpret_cast<char*>(lds_raw) + wave * 1024;
+        const int voff = (int)threadIdx.x * 16;
+#pragma unroll
+        for (int k = 0; k < PIECES; ++k)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(crs, (gsdr_lvoid*)(dst + k * PIECE), 16, voff,
+                qn * (int)(N * 8) + k * PIECE, 0, 0);
+    };
+    if constexpr (STAGED)
+        {
+            stage_code(0);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
     for (int q = 0; q < np; ++q)
         {
             {
                     float rmax = 0.0f, sum = 0.0f;
+                    if constexpr (STAGED)
+                        {
+                            // the X values that are not resident, issued ahead of the
+                            // first stage's LDS reads (fenced: the scheduler sank the
+                            // last of them behind the products, a second exposed wait)
+#pragma unroll
+                            for (int bb = 0; bb < BPT1; ++bb)
+                                {
+                                    const int jj = min((int)threadIdx.x + bb * NT, NB1 - 1);
+#pragma unroll
+                                    for (int r = R1 - XT; r < R1; ++r) xr[bb][r] = bload(xrs, jj * 8, r * NB1 * 8);
+                                }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
                     auto load = [&](int bb, int r, int i) -> c2 {
                         if constexpr (PREFETCH)
                             return gsdr::pk::conj_mul(xr[bb][r], cr[bb][r]);
+                        else if constexpr (STAGED)
+                            {
+                                // the resident products first, while the others' X values arrive
+                                if (XT > 0 && r == R1 - XT) __builtin_amdgcn_sched_barrier(0);
+                                return gsdr::pk::conj_mul(xr[bb][r], lds[i]);
+                            }
                         else
                             return gsdr::pk::conj_mul(xr[bb][r], bload(crs, i * 8, (int)(q * N * 8)));
                     };
@@ -483,7 +565,18 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                         rmax = __builtin_fmaxf(rmax, m);
                         if constexpr (STAT == 1) sum += m;
                     };
-                    MP::template run<false>(lds, tw, load, store, hook);
+                    if constexpr (STAGED)
+                        {
+                            // every wave has read its code values before any overwrites the buffer
+                            auto pre = [&]() { __syncthreads(); };
+                            // the buffer is dead: the next code row into it, under the butterflies
+                            auto mid = [&]() {
+                                if (q + 1 < np) stage_code(q + 1);
+                            };
+                            MP::template run<false>(lds, tw, load, store, hook, pre, mid);
+                        }
+                    else
+                        MP::template run<false>(lds, tw, load, store, hook);
                     rmax = gsdr::wave_max(rmax);
                     if constexpr (STAT == 1)
                         {
@@ -493,6 +586,8 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                     RowStat* sc = scratch + (q & 1) * NW;
                     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
                     if (lane == 0) sc[wave] = RowStat{rmax, 0u, sum, 0};
+                    // the wave's own copies have landed; the barrier publishes the row
+                    if constexpr (STAGED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __syncthreads();
                     if (threadIdx.x == 0)
                         {

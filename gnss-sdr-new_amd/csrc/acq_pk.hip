@@ -22,19 +22,24 @@ using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // A variant (default_pk_variant; GSDR_ACQ_CORR_VARIANT selects one for tests): id,
 // plan, PRNs per workgroup, waves-per-EU hint, row statistic (1 max + sum with the
 // argmax recomputed for the selected row, 2 max only with the CFAR row sum by
-// Parseval -- see acq_correlate_pk_kernel) and, for 93 / 94, the register four-step
+// Parseval -- see acq_correlate_pk_kernel), the code source (CodeSrc) and, for 93 / 94, the register four-step
 // the correlate runs on instead (acq_correlate_reg_kernel, N = 16000, PRN-group-major
 // XCD walk).  The alternatives measured in
 // rounds 1-4 and removed: other radix orders, per-stage twiddle
 // tables (-23 %) and LDS root copies (-2.5 %), padded layouts, late or dropped
 // barriers, 5 waves per SIMD (with spills -19 %; without, the first-stage products
 // in two halves, -2 %), 3 / 2 workgroups per CU (-8 % / -26 %), per-wave atomic row
-// maxima (-2 %), multi-transform workgroups: variant 70 at 104 VGPRs runs 4
-// workgroups (16 waves) per CU, where the CU's issue, not latency, bounds it.
-template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void>
+// maxima (-2 %), multi-transform workgroups with both operand sets in VGPRs:
+// variant 70 at 104 VGPRs runs 4 workgroups (16 waves) per CU, where the CU's
+// issue, not latency, bounds it.  97 is 70's plan with X resident for 16 PRNs and
+// the code rows staged through the drained FFT buffer (kCodeLds, 126 VGPRs under
+// the 4-waves-per-SIMD hint, no scratch): +5 % on the C2 bench, bit-identical
+// results; 70 stays as its A/B partner and the tests' reference.  Groups of 4 and
+// 8 PRNs (95, 96) gained +2 % and +3 % and were removed.
+template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr>
 struct PkVariant
 {
-    static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST;
+    static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST, CS = CS_;
     using type = MP;
     using Reg = REG;
 };
@@ -42,7 +47,8 @@ using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1
     PkVariant<62, PkPlan<256, true, 20, 10, 10>, 1, 1, 1>,
     PkVariant<93, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan93>,
     PkVariant<94, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan94>,
-    PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>>;
+    PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>,
+    PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>>;
 
 // f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
 // internal error in a launch: setup accepted the handle's id).
@@ -74,8 +80,8 @@ int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStre
             }
         else
             {
-                const uint32_t groups = (v.nprn + pg_count(V::PG) - 1) / pg_count(V::PG);
-                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT>), dim3(nblocks * v.D * groups),
+                const uint32_t groups = (v.nprn + V::PG - 1) / V::PG;
+                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS>), dim3(nblocks * v.D * groups),
                     dim3(M::NT), a->corr_lds_bytes, s, a->d_X, v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
                     v.xm);
             }
@@ -123,8 +129,10 @@ int setup_corr_variant(gsdr_acq* a, int id)
                 gsdr::set_error("correlate variant %d is for N = %d, not %u", V::id, M::N, a->N);
                 return GSDR_E_UNSUPPORTED;
             }
-        a->corr_lds_bytes = M::lds_bytes() + (size_t)2 * (M::NT / 64) * sizeof(RowStat);
-        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT>, a->corr_lds_bytes);
+        // the correlate's FFT buffer (padded for kCodeLds) and two sets of per-wave row statistics;
+        // the argmax pass, scratch right after its N c2, fits in the same allocation
+        a->corr_lds_bytes = pk_fft_bytes<M, V::CS>() + (size_t)2 * (M::NT / 64) * sizeof(RowStat);
+        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS>, a->corr_lds_bytes);
         rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT>, a->corr_lds_bytes);
         for (int it : kItemTypes)
             rc |= with_item_type(it, [&](auto t) {

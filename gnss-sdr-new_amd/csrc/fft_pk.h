@@ -285,13 +285,41 @@ struct Dft<32> : DftCT<4, 8>
 // or an LDS copy of the middle stage's roots (-2.5 %), last-stage block padding
 // (modelled conflicts removed, no gain), the barrier moved behind the butterflies
 // or dropped before the last stage (within noise).
-template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, class Load, class Store, class Hook>
-__device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook)
+//
+// Two more caller hooks, both NoHook unless PkPlan::run is given them:
+//   pre(): before the first stage's LDS writes, after its butterflies, outside
+//          any per-lane guard (a caller that kept operands in the buffer puts its
+//          barrier here);
+//   mid(): in the last stage between its barrier and its butterflies -- every
+//          lane's inputs are in registers, the buffer is dead until the next
+//          transform's first stage writes it.
+struct NoHook
+{
+    __device__ __forceinline__ void operator()() const {}
+};
+
+template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, class Load, class Store, class Hook,
+    class Pre, class Mid>
+__device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
+    Pre& pre, Mid& mid)
 {
     constexpr int BPT = fft::bpt_for(R);
+    // with a pre() hook the first stage's writes follow every pass's butterflies
+    constexpr bool PRE = FIRST && !LAST && !std::is_same<Pre, NoHook>::value;
+    // with a mid() hook the last stage's twiddle roots are loaded ahead of its
+    // barrier: a load issued after the hook's would wait for them too (vmcnt counts
+    // in order)
+    constexpr bool MID = LAST && !FIRST && TWP && !std::is_same<Mid, NoHook>::value;
     constexpr int NB = N / R;
     constexpr int TSTRIDE = N / (Ns * R);
     c2 v[BPT][R];
+    c2 w1[BPT];
+    if constexpr (MID)
+        {
+            // (every lane, the idle ones from a clamped index: no branch)
+#pragma unroll
+            for (int b = 0; b < BPT; ++b) w1[b] = from(tw[(min(threadIdx.x + (unsigned)(b * NT), (unsigned)(NB - 1)) % Ns) * TSTRIDE]);
+        }
 #pragma unroll
     for (int b = 0; b < BPT; ++b)
         {
@@ -327,7 +355,16 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
     if constexpr (FIRST)
         hook();
     else
-        __syncthreads();
+        {
+            if constexpr (MID)
+                {
+                    // the roots have arrived before the barrier, so before mid()
+#pragma unroll
+                    for (int b = 0; b < BPT; ++b) asm volatile("" : "+v"(w1[b]));
+                }
+            __syncthreads();
+            if constexpr (LAST) mid();
+        }
 #pragma unroll
     for (int b = 0; b < BPT; ++b)
         {
@@ -339,7 +376,9 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
                         {
                             k = j % Ns;
                             const int step = k * TSTRIDE;
-                            if constexpr (TWP)
+                            if constexpr (MID)
+                                apply_powers<R>(v[b], w1[b]);
+                            else if constexpr (TWP)
                                 apply_powers<R>(v[b], from(tw[step]));
                             else
                                 {
@@ -348,12 +387,27 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
                                 }
                         }
                     Dft<R>::run(v[b]);
-                    if constexpr (!LAST)
+                    if constexpr (!LAST && !PRE)
                         {
                             // block (j - k) R / (Ns R) = j / Ns of the last stage's input
                             const int base = (j - k) * R + k;
 #pragma unroll
                             for (int r = 0; r < R; ++r) lds[base + r * Ns] = v[b][r];
+                        }
+                }
+        }
+    if constexpr (PRE)
+        {
+            pre();
+#pragma unroll
+            for (int b = 0; b < BPT; ++b)
+                {
+                    const int j = (int)threadIdx.x + b * NT;
+                    if (NB % NT == 0 || j < NB)
+                        {
+                            // first stage: Ns = 1, k = 0
+#pragma unroll
+                            for (int r = 0; r < R; ++r) lds[j * R + r * Ns] = v[b][r];
                         }
                 }
         }
@@ -392,18 +446,21 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
         __syncthreads();
 }
 
-template <int NT, int N, int Ns, bool TWP, bool FIRST, bool ORD, int R, int... Rest, class Load, class Store, class Hook>
-__device__ __forceinline__ void stages(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook)
+template <int NT, int N, int Ns, bool TWP, bool FIRST, bool ORD, int R, int... Rest, class Load, class Store, class Hook,
+    class Pre, class Mid>
+__device__ __forceinline__ void stages(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
+    Pre& pre, Mid& mid)
 {
     constexpr bool LAST = sizeof...(Rest) == 0;
-    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD>(lds, tw, load, store, hook);
-    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, Rest...>(lds, tw, load, store, hook);
+    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD>(lds, tw, load, store, hook, pre, mid);
+    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, Rest...>(lds, tw, load, store, hook, pre, mid);
 }
 
 // Compile-time packed plan.  load(b, r, i) -> c2 returns input element i
 // (= j + r*N/R1 of this lane's b-th first-stage butterfly j); store(i, c2)
 // consumes output element i, visited in increasing i per lane; hook() runs
-// once the first stage's inputs are in registers (before its butterflies).
+// once the first stage's inputs are in registers (before its butterflies);
+// pre() and mid() are stage()'s optional hooks.
 //   TWP: inter-stage twiddles as powers of one loaded root (1) or R-1 loads (0).
 template <int NT_, int TWP_, int... Rs>
 struct PkPlan
@@ -426,10 +483,11 @@ struct PkPlan
     {
         return (int)threadIdx.x + (slot % BPTL) * NT + (slot / BPTL) * NSL;
     }
-    template <bool ORD = true, class Load, class Store, class Hook>
-    __device__ __forceinline__ static void run(c2* lds, const float2* __restrict__ tw, Load load, Store store, Hook hook)
+    template <bool ORD = true, class Load, class Store, class Hook, class Pre = NoHook, class Mid = NoHook>
+    __device__ __forceinline__ static void run(c2* lds, const float2* __restrict__ tw, Load load, Store store, Hook hook,
+        Pre pre = Pre{}, Mid mid = Mid{})
     {
-        stages<NT, N, 1, TWP, true, ORD, Rs...>(lds, tw, load, store, hook);
+        stages<NT, N, 1, TWP, true, ORD, Rs...>(lds, tw, load, store, hook, pre, mid);
     }
 };
 
