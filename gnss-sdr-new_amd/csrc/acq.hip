@@ -73,7 +73,10 @@ int code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
     AcqOp op{AcqOp::CodeFft};
     op.first_slot = first_slot;
     op.nslots = nslots;
-    return dispatch(a, view_of(a), op);
+    const int rc = dispatch(a, view_of(a), op);
+    // the refreshed slots' lane-order copies, behind their spectra on the handle's stream
+    if (rc != GSDR_OK || !a->d_code_lane) return rc;
+    return launch_code_lane_order(a, first_slot, nslots);
 }
 
 // update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), float arithmetic:
@@ -234,6 +237,7 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
     if (e == hipSuccess) e = hipMalloc(&a->d_tw, (size_t)N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_wipe, (size_t)a->D * N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_code_fft, nP * N * sizeof(float2));
+    if (e == hipSuccess && a->lane_nb1 > 0) e = hipMalloc(&a->d_code_lane, nP * N * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_code_stage, nP * a->consumed * sizeof(float2));
     if (e == hipSuccess) e = hipMalloc(&a->d_prn, nP * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&a->d_X, nB * a->K * a->D * N * sizeof(float2));
@@ -305,7 +309,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
             if (a->sub_done[i]) (void)hipEventDestroy(a->sub_done[i]);
             if (a->h_res[i]) (void)hipHostFree(a->h_res[i]);
         }
-    void* bufs[] = {a->st2.d_wipe, a->st2.d_freq, a->d_tw, a->d_wipe, a->d_code_fft, a->d_code_stage, a->d_prn, a->d_X, a->d_stats, a->d_res,
+    void* bufs[] = {a->st2.d_wipe, a->st2.d_freq, a->d_tw, a->d_wipe, a->d_code_fft, a->d_code_lane, a->d_code_stage, a->d_prn, a->d_X, a->d_stats, a->d_res,
         a->d_iq, a->d_grid, a->d_rowbuf, a->d_keys, a->d_psum, a->d_fscratch, a->d_dgrid, a->d_tw_sub, a->d_scratch, a->d_slots, a->d_resk, a->d_acc, a->d_acc_slots};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
@@ -621,6 +625,7 @@ int gsdr_acq_dump_grid_step_two(gsdr_acq* a, const void* iq_host, uint32_t prn_s
     v.nprn = 1;
     v.wipe = a->st2.d_wipe;
     v.code_fft = a->d_code_fft + (size_t)prn_slot * a->N;
+    v.code_lane = a->d_code_lane ? a->d_code_lane + (size_t)prn_slot * a->N : nullptr;
     v.xm = XMap{nb, 0u, a->N};
     rc = dispatch(a, v, AcqOp{AcqOp::DumpGrid});
     if (rc != GSDR_OK) return rc;
@@ -689,7 +694,7 @@ int gsdr_acq_run_step_two(gsdr_acq* a, const void* iq_host, uint32_t nsel, const
     for (uint32_t i = 0; i < nsel && rc == GSDR_OK; ++i)
         {
             const AcqView v{nb, 1, a->st2.d_wipe + (size_t)i * nb * a->N, a->d_code_fft + (size_t)prn_slots[i] * a->N,
-                a->d_prn + prn_slots[i], XMap{nb, 0u, a->N}, true, doppler_center_hz[i], coarse_input_power[i], thr};
+                a->d_code_lane ? a->d_code_lane + (size_t)prn_slots[i] * a->N : nullptr, a->d_prn + prn_slots[i], XMap{nb, 0u, a->N}, true, doppler_center_hz[i], coarse_input_power[i], thr};
             rc = run_blocks(a, v, a->d_iq, 1, a->consumed, stamp, a->d_res + i, a->stream);
         }
     if (rc != GSDR_OK) return rc;

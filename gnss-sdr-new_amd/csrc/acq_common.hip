@@ -220,6 +220,17 @@ __global__ void acq_decide_kernel(const gsdr_acq_result* __restrict__ resk, gsdr
     res[bp] = resk[(size_t)bp * K + k];
 }
 
+// The lane-order copy of code spectra (lane_order_slot): element i of a row to slot
+// s(i) of the same row of dst.  One workgroup per row; the values are copied, not
+// recomputed.
+__global__ void __launch_bounds__(256) acq_code_lane_order_kernel(const float2* __restrict__ src,
+    float2* __restrict__ dst, uint32_t N, int nb1, int r1)
+{
+    const float2* in = src + (size_t)blockIdx.x * N;
+    float2* out = dst + (size_t)blockIdx.x * N;
+    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) out[lane_order_slot((int)i, nb1, r1)] = in[i];
+}
+
 // first_vs_second_peak_statistic (:546-612) on the accumulated grid: row d* with
 // the +-samples_per_chip window zeroed (wrap at d_fft_size, :580-590), first
 // maximum of the rest.  One workgroup per PRN.
@@ -384,7 +395,7 @@ AcqEnv read_acq_env()
 // The main grid's view: every Doppler row and active PRN of the handle.
 AcqView view_of(const gsdr_acq* a)
 {
-    return AcqView{a->D, a->nprn, a->d_wipe, a->d_code_fft, a->d_prn, a->xm, false, 0.0f, 0.0f, 0.0f};
+    return AcqView{a->D, a->nprn, a->d_wipe, a->d_code_fft, a->d_code_lane, a->d_prn, a->xm, false, 0.0f, 0.0f, 0.0f};
 }
 
 AcqParams params_of(const gsdr_acq* a, const AcqView& v)
@@ -486,6 +497,16 @@ int launch_reduce(gsdr_acq* a, const AcqParams& ap, bool dwells, uint32_t nblock
 int launch_decide(gsdr_acq* a, uint32_t n, gsdr_acq_result* res, hipStream_t s)
 {
     hipLaunchKernelGGL(acq_decide_kernel, dim3((n + 255) / 256), dim3(256), 0, s, a->d_resk, res, a->K, n);
+    GSDR_HIP(hipGetLastError());
+    return GSDR_OK;
+}
+
+// Slots [first_slot, first_slot + nslots) of d_code_fft into d_code_lane.
+int launch_code_lane_order(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
+{
+    const size_t off = (size_t)first_slot * a->N;
+    hipLaunchKernelGGL(acq_code_lane_order_kernel, dim3(nslots), dim3(256), 0, a->stream, a->d_code_fft + off,
+        a->d_code_lane + off, a->N, a->lane_nb1, a->lane_r1);
     GSDR_HIP(hipGetLastError());
     return GSDR_OK;
 }

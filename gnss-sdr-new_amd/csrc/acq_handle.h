@@ -41,6 +41,7 @@ struct gsdr_acq
     int split{0};             // >0: the single-dwell split register four-step correlate (acq_split.hip)
     int corr_stat{0};         // the variant's row statistic (1/2: argmax recomputed by acq_argmax_pk_kernel)
     size_t corr_lds_bytes{0};
+    int lane_nb1{0}, lane_r1{0};  // the variant's correlate reads d_code_lane: its first stage's butterflies and radix
     gsdr::fft::Plan plan{};
     gsdr::fft::Plan4 plan4{};  // four-step plan (variants 20-27, N beyond one workgroup's LDS)
     size_t lds_bytes{0};
@@ -48,6 +49,7 @@ struct gsdr_acq
     float2* d_tw{nullptr};
     float2* d_wipe{nullptr};
     float2* d_code_fft{nullptr};
+    float2* d_code_lane{nullptr};  // the same rows in first-stage lane order (lane_order_slot), variants with lane_nb1 > 0
     float2* d_code_stage{nullptr};
     uint32_t* d_prn{nullptr};
     uint32_t nprn{0};
@@ -105,6 +107,7 @@ struct AcqView
     uint32_t D, nprn;
     const float2* wipe;      // D wipe-off rows (xm.q of them with the spectrum reuse)
     const float2* code_fft;  // nprn code spectra
+    const float2* code_lane; // the same rows in lane order (null unless the handle keeps them)
     const uint32_t* prn;     // their PRN ids
     XMap xm;
     // make_two_steps narrow grid (AcqParams::step_two ...)
@@ -137,7 +140,7 @@ inline int default_pk_variant(uint32_t N)
 {
     switch (N)
         {
-        case 4000: return 97;  // X resident for 16 PRNs, code rows by LDS DMA: +5 % over 70
+        case 4000: return 98;  // 97 with the code rows in first-stage lane order: +5 % over 97
         case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
         case 8000: return 61;
         case 2000: return 62;
@@ -177,6 +180,7 @@ int launch_reduce(gsdr_acq* a, const AcqParams& ap, bool dwells, uint32_t nblock
     const uint32_t* prn, uint64_t stamp0, uint64_t stride, hipStream_t s);
 int launch_decide(gsdr_acq* a, uint32_t n, gsdr_acq_result* res, hipStream_t s);
 int launch_grid_second_peak(gsdr_acq* a, const AcqParams& ap, gsdr_acq_result* res, hipStream_t s);
+int launch_code_lane_order(gsdr_acq* a, uint32_t first_slot, uint32_t nslots);
 
 // acq_pk.hip
 int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStream_t s);

@@ -403,19 +403,47 @@ __global__ void __launch_bounds__(PT::NT) acq_correlate_kernel(const float2* __r
 //                up to NW KiB (pk_fft_bytes) and the statistics scratch follows it.
 //                Same operands, product form and order as the other two: the row
 //                maxima are bit-identical.
+//   kCodeLane    kCodeLds with the copies taken from the handle's lane-order rows
+//                (lane_order_slot: still linear 1 KiB pieces, the LDS image equals
+//                the global layout): lane j's R1 code values lie in the slots
+//                j R1 + r that its own first-stage outputs go to.  A lane overwrites
+//                only what it alone has read and a wave's LDS operations execute in
+//                order, so there is no pre() barrier (5 per transform) and the stage
+//                takes fft_pk.h's ordinary write path.  With the outputs no longer
+//                all live across a barrier every X value stays resident (XT = 0) and
+//                the code values are read five at a time, a group ahead of their
+//                products; the wave without a first-stage butterfly skips the reads
+//                and products (SKIPW of fft_pk.h).  Operands, product form and order
+//                are unchanged again.
 enum CodeSrc
 {
     kCodeVgpr = 0,
     kCodeDirect = 1,
-    kCodeLds = 2
+    kCodeLds = 2,
+    kCodeLane = 3
 };
+
+// Lane order of a row for a first stage of nb1 butterflies of radix r1: input
+// r of butterfly j, element i = j + nb1 r, at slot j r1 + r -- where the stage writes
+// output r of butterfly j.
+constexpr int lane_order_slot(int i, int nb1, int r1) { return (i % nb1) * r1 + i / nb1; }
+// the map has an inverse on [0, nb1 r1) that stays inside it: a bijection
+constexpr bool lane_order_bijective(int nb1, int r1)
+{
+    for (int i = 0; i < nb1 * r1; ++i)
+        {
+            const int s = lane_order_slot(i, nb1, r1);
+            if (s < 0 || s >= nb1 * r1 || (s % r1) * nb1 + s / r1 != i) return false;
+        }
+    return true;
+}
 
 // bytes of the FFT buffer in front of the kernel's statistics scratch
 template <class MP, int CS>
 constexpr size_t pk_fft_bytes()
 {
     constexpr size_t piece = (size_t)(MP::NT / 64) * 1024;
-    return CS == kCodeLds ? (MP::lds_bytes() + piece - 1) / piece * piece : MP::lds_bytes();
+    return CS == kCodeLds || CS == kCodeLane ? (MP::lds_bytes() + piece - 1) / piece * piece : MP::lds_bytes();
 }
 
 template <class MP, int PG, int WPE, int STAT, int CS>
@@ -424,14 +452,19 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     uint32_t P, uint32_t nblocks, XMap xm)
 {
     static_assert(PG > 0, "PRN group");
-    static_assert(CS == kCodeVgpr || CS == kCodeDirect || CS == kCodeLds, "code source");
+    static_assert(CS == kCodeVgpr || CS == kCodeDirect || CS == kCodeLds || CS == kCodeLane, "code source");
     constexpr bool PREFETCH = CS == kCodeVgpr;
-    constexpr bool STAGED = CS == kCodeLds;
+    constexpr bool LANE = CS == kCodeLane;
+    constexpr bool STAGED = CS == kCodeLds || LANE;
+    static_assert(!LANE || (MP::BPT1 == 1 && lane_order_bijective(MP::NB1, MP::R1)), "lane order of the first stage");
     // kCodeLds: the last XT of the lane's R1 X values are not resident either: all
     // R1 of them beside the last stage's two passes and the first radix's working
     // set do not fit the 128 VGPRs of four workgroups per CU (the compiler spilled
     // 10), so the first stage loads those itself, as kCodeDirect loads the code.
-    constexpr int XT = STAGED ? (MP::R1 + 4) / 5 : 0;
+    // kCodeLane holds all R1 (its outputs are not all live across a barrier).
+    constexpr int XT = CS == kCodeLds ? (MP::R1 + 4) / 5 : 0;
+    // kCodeLane: the code values are read RA at a time, one group ahead of its products
+    constexpr int RA = LANE ? 5 : 0;
     static_assert(STAT == 1 || STAT == 2, "row statistic 1 (max + sum) or 2 (max)");
     using gsdr::pk::c2;
     constexpr int NT = MP::NT;
@@ -518,7 +551,7 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
         {
             {
                     float rmax = 0.0f, sum = 0.0f;
-                    if constexpr (STAGED)
+                    if constexpr (XT > 0)
                         {
                             // the X values that are not resident, issued ahead of the
                             // first stage's LDS reads (fenced: the scheduler sank the
@@ -532,6 +565,7 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                                 }
                             __builtin_amdgcn_sched_barrier(0);
                         }
+                    c2 cb[2][RA > 0 ? RA : 1];
                     auto load = [&](int bb, int r, int i) -> c2 {
                         if constexpr (PREFETCH)
                             return gsdr::pk::conj_mul(xr[bb][r], cr[bb][r]);
@@ -539,6 +573,28 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                             {
                                 // the resident products first, while the others' X values arrive
                                 if (XT > 0 && r == R1 - XT) __builtin_amdgcn_sched_barrier(0);
+                                // kCodeLane: the lane's own output slots (an idle lane of a
+                                // half-filled wave reads the last butterfly's, as it loads its X),
+                                // group g + 1 issued before group g's products, fenced so
+                                // that the scheduler keeps the reads ahead
+                                if constexpr (LANE)
+                                    {
+                                        const c2* row = lds + min((int)threadIdx.x, NB1 - 1) * R1;
+                                        if (r % RA == 0)
+                                            {
+                                                if (r == 0)
+                                                    {
+#pragma unroll
+                                                        for (int k = 0; k < RA; ++k) cb[0][k] = row[k];
+                                                    }
+                                                const int g = r / RA + 1;
+#pragma unroll
+                                                for (int k = 0; k < RA; ++k)
+                                                    if (g * RA + k < R1) cb[g & 1][k] = row[g * RA + k];
+                                                __builtin_amdgcn_sched_barrier(0);
+                                            }
+                                        return gsdr::pk::conj_mul(xr[bb][r], cb[(r / RA) & 1][r % RA]);
+                                    }
                                 return gsdr::pk::conj_mul(xr[bb][r], lds[i]);
                             }
                         else
@@ -573,7 +629,10 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                             auto mid = [&]() {
                                 if (q + 1 < np) stage_code(q + 1);
                             };
-                            MP::template run<false>(lds, tw, load, store, hook, pre, mid);
+                            if constexpr (LANE)
+                                MP::template run<false, true>(lds, tw, load, store, hook, gsdr::pk::NoHook{}, mid);
+                            else
+                                MP::template run<false>(lds, tw, load, store, hook, pre, mid);
                         }
                     else
                         MP::template run<false>(lds, tw, load, store, hook);

@@ -34,8 +34,16 @@ using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // issue, not latency, bounds it.  97 is 70's plan with X resident for 16 PRNs and
 // the code rows staged through the drained FFT buffer (kCodeLds, 126 VGPRs under
 // the 4-waves-per-SIMD hint, no scratch): +5 % on the C2 bench, bit-identical
-// results; 70 stays as its A/B partner and the tests' reference.  Groups of 4 and
-// 8 PRNs (95, 96) gained +2 % and +3 % and were removed.
+// results; 70 stays as the tests' reference.  Groups of 4 and 8 PRNs (95, 96) gained
+// +2 % and +3 % and were removed.  98 is 97 with the code rows copied from the
+// handle's lane-order buffer (kCodeLane: each lane's 25 code values in its own output
+// slots, so no barrier before the first stage's writes -- 5 per transform instead of
+// 6 --, all 25 X values resident, code reads five ahead of their products, the idle
+// wave skipping the first stage's reads and products; 128 VGPRs, no scratch,
+// occupancy 4): +5 % over 97 on the C2 bench, bit-identical results; 97 stays as its
+// A/B partner.  Measured on the way and not kept: the five reloaded X
+// values kept (+3.5 % over 97), reads three ahead, the reads as single ds_read_b64 in inline
+// assembly with counted lgkmcnt waits.
 template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr>
 struct PkVariant
 {
@@ -48,7 +56,8 @@ using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1
     PkVariant<93, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan93>,
     PkVariant<94, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan94>,
     PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>,
-    PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>>;
+    PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>,
+    PkVariant<98, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane>>;
 
 // f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
 // internal error in a launch: setup accepted the handle's id).
@@ -82,7 +91,7 @@ int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStre
             {
                 const uint32_t groups = (v.nprn + V::PG - 1) / V::PG;
                 hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS>), dim3(nblocks * v.D * groups),
-                    dim3(M::NT), a->corr_lds_bytes, s, a->d_X, v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
+                    dim3(M::NT), a->corr_lds_bytes, s, a->d_X, V::CS == kCodeLane ? v.code_lane : v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
                     v.xm);
             }
         return GSDR_OK;
@@ -142,6 +151,8 @@ int setup_corr_variant(gsdr_acq* a, int id)
             rc |= set_max_lds((const void*)acq_correlate_reg_kernel<typename V::Reg>, V::Reg::lds_bytes());
         if (rc != GSDR_OK) return GSDR_E_DEVICE;
         a->corr_variant = V::id;
+        a->lane_nb1 = V::CS == kCodeLane ? M::NB1 : 0;
+        a->lane_r1 = V::CS == kCodeLane ? M::R1 : 0;
         a->corr_stat = V::STAT;
         return GSDR_OK;
     }, GSDR_OK);

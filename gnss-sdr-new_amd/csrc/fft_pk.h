@@ -298,8 +298,8 @@ struct NoHook
     __device__ __forceinline__ void operator()() const {}
 };
 
-template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, class Load, class Store, class Hook,
-    class Pre, class Mid>
+template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, bool SKIPW, class Load, class Store,
+    class Hook, class Pre, class Mid>
 __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
     Pre& pre, Mid& mid)
 {
@@ -331,13 +331,18 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
             if constexpr (BPT == 1 && NB % NT != 0)
                 {
                     const int jj = min(j, NB - 1);
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
+                    // SKIPW: a wave without any butterfly of the first stage skips its loads
+                    // (and whatever the load functor computes) on a wave-uniform branch
+                    if (!FIRST || !SKIPW || __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) < NB)
                         {
-                            if constexpr (FIRST)
-                                v[b][r] = load(b, r, jj + r * NB);
-                            else
-                                v[b][r] = lds[jj + r * NB];
+#pragma unroll
+                            for (int r = 0; r < R; ++r)
+                                {
+                                    if constexpr (FIRST)
+                                        v[b][r] = load(b, r, jj + r * NB);
+                                    else
+                                        v[b][r] = lds[jj + r * NB];
+                                }
                         }
                 }
             else if (NB % NT == 0 || j < NB)
@@ -446,21 +451,22 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
         __syncthreads();
 }
 
-template <int NT, int N, int Ns, bool TWP, bool FIRST, bool ORD, int R, int... Rest, class Load, class Store, class Hook,
-    class Pre, class Mid>
+template <int NT, int N, int Ns, bool TWP, bool FIRST, bool ORD, bool SKIPW, int R, int... Rest, class Load, class Store,
+    class Hook, class Pre, class Mid>
 __device__ __forceinline__ void stages(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
     Pre& pre, Mid& mid)
 {
     constexpr bool LAST = sizeof...(Rest) == 0;
-    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD>(lds, tw, load, store, hook, pre, mid);
-    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, Rest...>(lds, tw, load, store, hook, pre, mid);
+    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD, SKIPW>(lds, tw, load, store, hook, pre, mid);
+    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, SKIPW, Rest...>(lds, tw, load, store, hook, pre, mid);
 }
 
 // Compile-time packed plan.  load(b, r, i) -> c2 returns input element i
 // (= j + r*N/R1 of this lane's b-th first-stage butterfly j); store(i, c2)
 // consumes output element i, visited in increasing i per lane; hook() runs
 // once the first stage's inputs are in registers (before its butterflies);
-// pre() and mid() are stage()'s optional hooks.
+// pre() and mid() are stage()'s optional hooks, SKIPW its switch for a first stage
+// that leaves whole waves without a butterfly.
 //   TWP: inter-stage twiddles as powers of one loaded root (1) or R-1 loads (0).
 template <int NT_, int TWP_, int... Rs>
 struct PkPlan
@@ -483,11 +489,11 @@ struct PkPlan
     {
         return (int)threadIdx.x + (slot % BPTL) * NT + (slot / BPTL) * NSL;
     }
-    template <bool ORD = true, class Load, class Store, class Hook, class Pre = NoHook, class Mid = NoHook>
+    template <bool ORD = true, bool SKIPW = false, class Load, class Store, class Hook, class Pre = NoHook, class Mid = NoHook>
     __device__ __forceinline__ static void run(c2* lds, const float2* __restrict__ tw, Load load, Store store, Hook hook,
         Pre pre = Pre{}, Mid mid = Mid{})
     {
-        stages<NT, N, 1, TWP, true, ORD, Rs...>(lds, tw, load, store, hook, pre, mid);
+        stages<NT, N, 1, TWP, true, ORD, SKIPW, Rs...>(lds, tw, load, store, hook, pre, mid);
     }
 };
 
