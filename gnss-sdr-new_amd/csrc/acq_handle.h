@@ -140,7 +140,7 @@ inline int default_pk_variant(uint32_t N)
 {
     switch (N)
         {
-        case 4000: return 98;  // 97 with the code rows in first-stage lane order: +5 % over 97
+        case 4000: return 99;  // 98 with the twiddle powers and roots from per-workgroup LDS tables: +1.2 % over 98
         case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
         case 8000: return 61;
         case 2000: return 62;

@@ -446,16 +446,118 @@ constexpr size_t pk_fft_bytes()
     return CS == kCodeLds || CS == kCodeLane ? (MP::lds_bytes() + piece - 1) / piece * piece : MP::lds_bytes();
 }
 
-template <class MP, int PG, int WPE, int STAT, int CS>
+// Where the inter-stage twiddles of a three-stage plan R1 x R2 x RL come from (TW):
+//   kTwGlobal  the handle's table tw, a root per butterfly (fft_pk.h TWP): a global
+//              load and its wait in every transform, and the power chain w^2 .. of
+//              the middle stage recomputed in every transform;
+//   kTwLds     two tables in the workgroup's LDS behind the statistics scratch, built
+//              once per workgroup ahead of the barrier that publishes code row 0 and
+//              never written again.  The middle stage's holds the powers w^r of
+//              w = tw[k RL], r = 1 .. R2-1, k < R1, formed by apply_powers' own chain
+//              (the bits the registers held), r-major: lanes of equal k read one
+//              address, and the stage multiplies v[r] by its entry -- no chain, R2-2
+//              complex products fewer per butterfly.  The last stage's is a copy of
+//              its roots tw[0 .. R1 R2); it keeps its chain.  Both are read beside the
+//              stage's inputs, ahead of its barrier.
+// The factors are the same in both, so are the results.  Measured on the way and not
+// kept (profiles/tw99): the roots alone from LDS with both chains kept (within noise),
+// and the power table read as the ds_read2_b64 pairs the compiler forms (-2 %: the
+// pairs are banked mod 32, where the wrap of k at R1 = 25 makes two lanes of a
+// 16-lane group collide; the conflict cycles nearly doubled).
+enum TwSrc
+{
+    kTwGlobal = 0,
+    kTwLds = 1
+};
+
+// middle-stage table: entry of w^r (1 <= r < r2) for root k of ns2; its elements
+constexpr int tw_mid_index(int r, int k, int ns2) { return (r - 1) * ns2 + k; }
+constexpr int tw_mid_elems(int tw, int r2, int ns2) { return tw == kTwLds ? (r2 - 1) * ns2 : 0; }
+// last-stage table: a copy of tw[0 .. ns3)
+constexpr int tw_last_elems(int tw, int ns3) { return tw == kTwLds ? ns3 : 0; }
+
+// The correlate kernel's dynamic LDS: the FFT buffer, two sets of per-wave row
+// statistics, the twiddle tables (middle, then last).
+template <class MP, int CS>
+constexpr size_t pk_tw_offset()
+{
+    return pk_fft_bytes<MP, CS>() + (size_t)2 * (MP::NT / 64) * sizeof(RowStat);
+}
+template <class MP, int TW>
+constexpr size_t pk_tw_bytes()
+{
+    constexpr int R2 = MP::N / (MP::R1 * MP::RL);
+    return (size_t)(tw_mid_elems(TW, R2, MP::R1) + tw_last_elems(TW, MP::NSL)) * sizeof(gsdr::pk::c2);
+}
+template <class MP, int CS, int TW>
+constexpr size_t pk_corr_lds_bytes()
+{
+    return pk_tw_offset<MP, CS>() + pk_tw_bytes<MP, TW>();
+}
+
+// fft_pk.h twiddle source on those tables (middle stage of radix R2 after NS2 = R1)
+template <int R2, int NS2>
+struct TwLds
+{
+    const gsdr::pk::c2* mid;
+    const gsdr::pk::c2* last;
+    template <int R>
+    struct Mid
+    {
+        gsdr::pk::c2 w[R - 1];
+    };
+    // Single ds_read_b64 in inline assembly: banked mod 64, the NS2 <= 32 entries of a
+    // row never conflict and equal k broadcast.  The compiler does not count these
+    // reads, so middle() waits for them itself; they return in order with the
+    // compiler's own LDS reads, whose counted waits they can only lengthen.
+    template <int R, int I>
+    __device__ __forceinline__ static void read_powers(Mid<R>& m, unsigned a)
+    {
+        asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(m.w[I - 1]) : "v"(a), "n"(tw_mid_index(I, 0, NS2) * 8));
+        if constexpr (I + 1 < R) read_powers<R, I + 1>(m, a);
+    }
+    template <int R, int Ns>
+    __device__ __forceinline__ Mid<R> load_middle(int k) const
+    {
+        static_assert(R == R2 && Ns == NS2 && NS2 <= 32, "the plan's middle stage");
+        Mid<R> m;
+        read_powers<R, 1>(m, (unsigned)(uintptr_t)(gsdr_lvoid*)const_cast<gsdr::pk::c2*>(mid + k));
+        return m;
+    }
+    template <int R>
+    __device__ __forceinline__ void middle(gsdr::pk::c2* v, const Mid<R>& m) const
+    {
+        Mid<R> t = m;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int r = 1; r < R; ++r) asm volatile("" : "+v"(t.w[r - 1]));
+#pragma unroll
+        for (int r = 1; r < R; ++r) v[r] = gsdr::pk::mul(v[r], t.w[r - 1]);
+    }
+    __device__ __forceinline__ gsdr::pk::c2 last_root(int k) const { return last[k]; }
+};
+
+template <class MP, int PG, int WPE, int STAT, int CS, int TW = kTwGlobal>
 __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE))) acq_correlate_pk_kernel(const float2* __restrict__ X,
     const float2* __restrict__ code_fft, RowStat* __restrict__ stats, const float2* __restrict__ tw, uint32_t D,
     uint32_t P, uint32_t nblocks, XMap xm)
 {
     static_assert(PG > 0, "PRN group");
     static_assert(CS == kCodeVgpr || CS == kCodeDirect || CS == kCodeLds || CS == kCodeLane, "code source");
+    static_assert(TW == kTwGlobal || TW == kTwLds, "twiddle source");
     constexpr bool PREFETCH = CS == kCodeVgpr;
     constexpr bool LANE = CS == kCodeLane;
     constexpr bool STAGED = CS == kCodeLds || LANE;
+    constexpr bool TABLES = TW != kTwGlobal;
+    // the tables are published by the barrier behind stage_code(0), and lie beyond
+    // everything written later: the code rows' last piece ends with the padded
+    // buffer, the statistics scratch follows it
+    static_assert(!TABLES || (STAGED && MP::nstages == 3 && MP::TWP), "twiddle tables: a staged three-stage TWP plan");
+    static_assert(!STAGED || pk_fft_bytes<MP, CS>() % ((MP::NT / 64) * 1024) == 0, "whole pieces fill the padded buffer");
+    static_assert(pk_tw_offset<MP, CS>() >= pk_fft_bytes<MP, CS>() + 2 * (MP::NT / 64) * sizeof(RowStat), "tables behind the scratch");
+    static_assert(!TABLES || pk_tw_offset<MP, CS>() % sizeof(gsdr::pk::c2) == 0, "table alignment");
+    // four workgroups per CU: 160 KiB / 4
+    static_assert(!TABLES || pk_corr_lds_bytes<MP, CS, TW>() <= 40960, "LDS of four workgroups per CU");
     static_assert(!LANE || (MP::BPT1 == 1 && lane_order_bijective(MP::NB1, MP::R1)), "lane order of the first stage");
     // kCodeLds: the last XT of the lane's R1 X values are not resident either: all
     // R1 of them beside the last stage's two passes and the first radix's working
@@ -494,6 +596,16 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     const uint32_t b = row / D, d = row - (row / D) * D;
     const uint32_t p0 = g * PG;
     const int np = (int)min((uint32_t)PG, P - p0);
+    // the twiddle source: the tables behind the statistics scratch (built below)
+    constexpr int R2 = MP::N / (MP::R1 * MP::RL);
+    using Tws = std::conditional_t<TABLES, TwLds<R2, MP::R1>, gsdr::pk::TwGlobal>;
+    Tws tws{};
+    (void)tws;
+    if constexpr (TABLES)
+        {
+            tws.mid = lds + pk_tw_offset<MP, CS>() / sizeof(c2);
+            tws.last = tws.mid + tw_mid_elems(TW, R2, MP::R1);
+        }
     // the X row and the code spectra through buffer descriptors built from
     // wave-uniform values: per-lane byte offset j*8 in voffset, r*NB1*8 as the
     // scalar/immediate offset -- no 64-bit address arithmetic per load
@@ -544,6 +656,29 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     if constexpr (STAGED)
         {
             stage_code(0);
+            if constexpr (TABLES)
+                {
+                    // the twiddle tables, once per workgroup, their loads in flight beside the
+                    // X row's and code row 0's: every lane copies its share of the last
+                    // stage's roots, lane k < R1 runs apply_powers' chain on its middle-stage
+                    // root and stores each power.  The barrier that publishes code row 0
+                    // publishes them.
+                    c2* tmid = lds + pk_tw_offset<MP, CS>() / sizeof(c2);
+                    c2* tlast = tmid + tw_mid_elems(TW, R2, MP::R1);
+#pragma unroll
+                    for (int k = (int)threadIdx.x; k < MP::NSL; k += NT) tlast[k] = gsdr::pk::from(tw[k]);
+                    for (int k = (int)threadIdx.x; k < MP::R1; k += NT)
+                        {
+                            const c2 w1 = gsdr::pk::from(tw[k * MP::RL]);
+                            c2 w = w1;
+#pragma unroll
+                            for (int r = 1; r < R2; ++r)
+                                {
+                                    if (r > 1) w = gsdr::pk::mul(w, w1);
+                                    tmid[tw_mid_index(r, k, MP::R1)] = w;
+                                }
+                        }
+                }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
@@ -630,7 +765,7 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                                 if (q + 1 < np) stage_code(q + 1);
                             };
                             if constexpr (LANE)
-                                MP::template run<false, true>(lds, tw, load, store, hook, gsdr::pk::NoHook{}, mid);
+                                MP::template run<false, true>(lds, tw, load, store, hook, gsdr::pk::NoHook{}, mid, tws);
                             else
                                 MP::template run<false>(lds, tw, load, store, hook, pre, mid);
                         }

@@ -43,11 +43,16 @@ using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // occupancy 4): +5 % over 97 on the C2 bench, bit-identical results; 97 stays as its
 // A/B partner.  Measured on the way and not kept: the five reloaded X
 // values kept (+3.5 % over 97), reads three ahead, the reads as single ds_read_b64 in inline
-// assembly with counted lgkmcnt waits.
-template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr>
+// assembly with counted lgkmcnt waits.  99 is 98 with the inter-stage twiddles from two
+// tables in the workgroup's LDS (kTwLds of acq_kernels.h: the middle stage's powers w^r and
+// the last stage's roots, built once per workgroup, read ahead of each stage's barrier --
+// no global load left in a transform but the code-row copies, 28 packed products fewer per
+// wave; 126 VGPRs, no scratch, occupancy 4, 39,096 B of LDS): +1.2 % over 98 on the C2
+// bench, bit-identical results; 98 stays as its A/B partner.
+template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr, int TW_ = kTwGlobal>
 struct PkVariant
 {
-    static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST, CS = CS_;
+    static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST, CS = CS_, TW = TW_;
     using type = MP;
     using Reg = REG;
 };
@@ -57,7 +62,8 @@ using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1
     PkVariant<94, PkPlan<1024, 1, 16, 10, 10, 10>, 1, 1, 2, RegPlan94>,
     PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>,
     PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>,
-    PkVariant<98, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane>>;
+    PkVariant<98, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane>,
+    PkVariant<99, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwLds>>;
 
 // f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
 // internal error in a launch: setup accepted the handle's id).
@@ -90,7 +96,7 @@ int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStre
         else
             {
                 const uint32_t groups = (v.nprn + V::PG - 1) / V::PG;
-                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS>), dim3(nblocks * v.D * groups),
+                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS, V::TW>), dim3(nblocks * v.D * groups),
                     dim3(M::NT), a->corr_lds_bytes, s, a->d_X, V::CS == kCodeLane ? v.code_lane : v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
                     v.xm);
             }
@@ -138,10 +144,11 @@ int setup_corr_variant(gsdr_acq* a, int id)
                 gsdr::set_error("correlate variant %d is for N = %d, not %u", V::id, M::N, a->N);
                 return GSDR_E_UNSUPPORTED;
             }
-        // the correlate's FFT buffer (padded for kCodeLds) and two sets of per-wave row statistics;
-        // the argmax pass, scratch right after its N c2, fits in the same allocation
-        a->corr_lds_bytes = pk_fft_bytes<M, V::CS>() + (size_t)2 * (M::NT / 64) * sizeof(RowStat);
-        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS>, a->corr_lds_bytes);
+        // the correlate's FFT buffer (padded for kCodeLds), two sets of per-wave row statistics and
+        // the variant's twiddle tables; the argmax pass, scratch right after its N c2, fits in the
+        // same allocation
+        a->corr_lds_bytes = pk_corr_lds_bytes<M, V::CS, V::TW>();
+        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS, V::TW>, a->corr_lds_bytes);
         rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT>, a->corr_lds_bytes);
         for (int it : kItemTypes)
             rc |= with_item_type(it, [&](auto t) {

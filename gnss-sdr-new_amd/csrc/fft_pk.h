@@ -298,22 +298,43 @@ struct NoHook
     __device__ __forceinline__ void operator()() const {}
 };
 
-template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, bool SKIPW, class Load, class Store,
-    class Hook, class Pre, class Mid>
-__device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
-    Pre& pre, Mid& mid)
+// Where the inter-stage twiddles come from.  TwGlobal: the table `tw` in global
+// memory, as TWP says (every caller's default).  Any other type is a caller's own
+// source of the same values (TWP plans only), e.g. tables in its LDS, read beside
+// the stage's inputs, ahead of its barrier:
+//   Mid<R>                  what a middle stage of radix R holds per butterfly;
+//   load_middle<R, Ns>(k)   -> Mid<R> for w = tw[k N / (Ns R)] -- a stage that is
+//                           neither the first nor the last;
+//   middle<R>(v, m)         v[r] *= w^r for r = 1 .. R-1, with the bits of
+//                           apply_powers' chain;
+//   last_root(k)            tw[k], the last stage's root; apply_powers runs on it.
+// Such a source needs no early global load ahead of the last stage's barrier (MID
+// below).
+struct TwGlobal
 {
+    template <int R>
+    using Mid = c2;
+};
+
+template <int R, int NT, int N, int Ns, bool TWP, bool FIRST, bool LAST, bool ORD, bool SKIPW, class Load, class Store,
+    class Hook, class Pre, class Mid, class Tws>
+__device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
+    Pre& pre, Mid& mid, const Tws& tws)
+{
+    constexpr bool GLOBAL = std::is_same<Tws, TwGlobal>::value;
+    static_assert(GLOBAL || TWP, "a twiddle source stands for the roots of a TWP plan");
     constexpr int BPT = fft::bpt_for(R);
     // with a pre() hook the first stage's writes follow every pass's butterflies
     constexpr bool PRE = FIRST && !LAST && !std::is_same<Pre, NoHook>::value;
     // with a mid() hook the last stage's twiddle roots are loaded ahead of its
     // barrier: a load issued after the hook's would wait for them too (vmcnt counts
     // in order)
-    constexpr bool MID = LAST && !FIRST && TWP && !std::is_same<Mid, NoHook>::value;
+    constexpr bool MID = LAST && !FIRST && TWP && GLOBAL && !std::is_same<Mid, NoHook>::value;
     constexpr int NB = N / R;
     constexpr int TSTRIDE = N / (Ns * R);
     c2 v[BPT][R];
     c2 w1[BPT];
+    std::conditional_t<LAST, c2, typename Tws::template Mid<R>> tf[BPT];
     if constexpr (MID)
         {
             // (every lane, the idle ones from a clamped index: no branch)
@@ -361,6 +382,19 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
         hook();
     else
         {
+            if constexpr (!GLOBAL)
+                {
+                    // (every lane, the idle ones from a clamped index)
+#pragma unroll
+                    for (int b = 0; b < BPT; ++b)
+                        {
+                            const int k = min((int)threadIdx.x + b * NT, NB - 1) % Ns;
+                            if constexpr (LAST)
+                                tf[b] = tws.last_root(k * TSTRIDE);
+                            else
+                                tf[b] = tws.template load_middle<R, Ns>(k);
+                        }
+                }
             if constexpr (MID)
                 {
                     // the roots have arrived before the barrier, so before mid()
@@ -381,7 +415,14 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
                         {
                             k = j % Ns;
                             const int step = k * TSTRIDE;
-                            if constexpr (MID)
+                            if constexpr (!GLOBAL)
+                                {
+                                    if constexpr (LAST)
+                                        apply_powers<R>(v[b], tf[b]);
+                                    else
+                                        tws.template middle<R>(v[b], tf[b]);
+                                }
+                            else if constexpr (MID)
                                 apply_powers<R>(v[b], w1[b]);
                             else if constexpr (TWP)
                                 apply_powers<R>(v[b], from(tw[step]));
@@ -452,13 +493,13 @@ __device__ __forceinline__ void stage(c2* lds, const float2* __restrict__ tw, Lo
 }
 
 template <int NT, int N, int Ns, bool TWP, bool FIRST, bool ORD, bool SKIPW, int R, int... Rest, class Load, class Store,
-    class Hook, class Pre, class Mid>
+    class Hook, class Pre, class Mid, class Tws>
 __device__ __forceinline__ void stages(c2* lds, const float2* __restrict__ tw, Load& load, Store& store, Hook& hook,
-    Pre& pre, Mid& mid)
+    Pre& pre, Mid& mid, const Tws& tws)
 {
     constexpr bool LAST = sizeof...(Rest) == 0;
-    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD, SKIPW>(lds, tw, load, store, hook, pre, mid);
-    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, SKIPW, Rest...>(lds, tw, load, store, hook, pre, mid);
+    stage<R, NT, N, Ns, TWP, FIRST, LAST, ORD, SKIPW>(lds, tw, load, store, hook, pre, mid, tws);
+    if constexpr (!LAST) stages<NT, N, Ns * R, TWP, false, ORD, SKIPW, Rest...>(lds, tw, load, store, hook, pre, mid, tws);
 }
 
 // Compile-time packed plan.  load(b, r, i) -> c2 returns input element i
@@ -466,7 +507,7 @@ __device__ __forceinline__ void stages(c2* lds, const float2* __restrict__ tw, L
 // consumes output element i, visited in increasing i per lane; hook() runs
 // once the first stage's inputs are in registers (before its butterflies);
 // pre() and mid() are stage()'s optional hooks, SKIPW its switch for a first stage
-// that leaves whole waves without a butterfly.
+// that leaves whole waves without a butterfly, tws its twiddle source (TwGlobal: tw).
 //   TWP: inter-stage twiddles as powers of one loaded root (1) or R-1 loads (0).
 template <int NT_, int TWP_, int... Rs>
 struct PkPlan
@@ -489,11 +530,12 @@ struct PkPlan
     {
         return (int)threadIdx.x + (slot % BPTL) * NT + (slot / BPTL) * NSL;
     }
-    template <bool ORD = true, bool SKIPW = false, class Load, class Store, class Hook, class Pre = NoHook, class Mid = NoHook>
+    template <bool ORD = true, bool SKIPW = false, class Load, class Store, class Hook, class Pre = NoHook, class Mid = NoHook,
+        class Tws = TwGlobal>
     __device__ __forceinline__ static void run(c2* lds, const float2* __restrict__ tw, Load load, Store store, Hook hook,
-        Pre pre = Pre{}, Mid mid = Mid{})
+        Pre pre = Pre{}, Mid mid = Mid{}, Tws tws = Tws{})
     {
-        stages<NT, N, 1, TWP, true, ORD, SKIPW, Rs...>(lds, tw, load, store, hook, pre, mid);
+        stages<NT, N, 1, TWP, true, ORD, SKIPW, Rs...>(lds, tw, load, store, hook, pre, mid, tws);
     }
 };
 
