@@ -600,6 +600,30 @@ int gsdr_acq_dump_grid(gsdr_acq* a, const void* iq_host, uint32_t prn_slot, floa
     return GSDR_OK;
 }
 
+int gsdr_acq_dump_row_maxima(gsdr_acq* a, const void* iq_host, float* out_host)
+{
+    GSDR_REQUIRE(a && iq_host && out_host, GSDR_E_ARG, "gsdr_acq_dump_row_maxima: null argument");
+    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_dump_row_maxima: set_local_codes first");
+    GSDR_REQUIRE(a->corr_variant > 0 && !a->general && a->split == 0, GSDR_E_UNSUPPORTED,
+        "gsdr_acq_dump_row_maxima: the handle runs no packed correlate variant");
+    std::lock_guard<std::mutex> lk(a->mu);
+    gsdr::DeviceGuard g(a->device);
+    const AcqView v = view_of(a);
+    GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)a->consumed * gsdr::item_bytes(a->conf.item_type),
+        hipMemcpyHostToDevice, a->stream));
+    int rc = launch_forward_pk(a, v, a->d_iq, 1, a->consumed, a->stream);
+    if (rc == GSDR_OK) rc = launch_corr_variant(a, v, 1, a->stream);
+    if (rc != GSDR_OK) return rc;
+    GSDR_HIP(hipGetLastError());
+    // stats[p D + d] of block 0
+    std::vector<RowStat> st((size_t)v.nprn * v.D);
+    GSDR_HIP(hipMemcpyAsync(st.data(), a->d_stats, st.size() * sizeof(RowStat), hipMemcpyDeviceToHost, a->stream));
+    GSDR_HIP(hipStreamSynchronize(a->stream));
+    for (uint32_t d = 0; d < v.D; ++d)
+        for (uint32_t p = 0; p < v.nprn; ++p) out_host[(size_t)d * v.nprn + p] = st[(size_t)p * v.D + d].max;
+    return GSDR_OK;
+}
+
 int gsdr_acq_dump_grid_step_two(gsdr_acq* a, const void* iq_host, uint32_t prn_slot, float doppler_center_hz,
     float* grid_host)
 {

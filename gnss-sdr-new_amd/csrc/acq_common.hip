@@ -220,15 +220,16 @@ __global__ void acq_decide_kernel(const gsdr_acq_result* __restrict__ resk, gsdr
     res[bp] = resk[(size_t)bp * K + k];
 }
 
-// The lane-order copy of code spectra (lane_order_slot): element i of a row to slot
-// s(i) of the same row of dst.  One workgroup per row; the values are copied, not
-// recomputed.
+// The lane-order copy of code spectra (lane_order_slot, or pfa_lane_order_slot for a
+// variant whose correlate runs the prime-factor plan): element i of a row to slot s(i) of
+// the same row of dst.  One workgroup per row; the values are copied, not recomputed.
 __global__ void __launch_bounds__(256) acq_code_lane_order_kernel(const float2* __restrict__ src,
-    float2* __restrict__ dst, uint32_t N, int nb1, int r1)
+    float2* __restrict__ dst, uint32_t N, int nb1, int r1, int pfa)
 {
     const float2* in = src + (size_t)blockIdx.x * N;
     float2* out = dst + (size_t)blockIdx.x * N;
-    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) out[lane_order_slot((int)i, nb1, r1)] = in[i];
+    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x)
+        out[pfa ? pfa_lane_order_slot((int)i) : lane_order_slot((int)i, nb1, r1)] = in[i];
 }
 
 // first_vs_second_peak_statistic (:546-612) on the accumulated grid: row d* with
@@ -506,7 +507,7 @@ int launch_code_lane_order(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
 {
     const size_t off = (size_t)first_slot * a->N;
     hipLaunchKernelGGL(acq_code_lane_order_kernel, dim3(nslots), dim3(256), 0, a->stream, a->d_code_fft + off,
-        a->d_code_lane + off, a->N, a->lane_nb1, a->lane_r1);
+        a->d_code_lane + off, a->N, a->lane_nb1, a->lane_r1, a->lane_pfa);
     GSDR_HIP(hipGetLastError());
     return GSDR_OK;
 }

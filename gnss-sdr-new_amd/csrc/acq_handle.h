@@ -42,6 +42,7 @@ struct gsdr_acq
     int corr_stat{0};         // the variant's row statistic (1/2: argmax recomputed by acq_argmax_pk_kernel)
     size_t corr_lds_bytes{0};
     int lane_nb1{0}, lane_r1{0};  // the variant's correlate reads d_code_lane: its first stage's butterflies and radix
+    int lane_pfa{0};              // ... in the prime-factor plan's order (pfa_lane_order_slot) instead of lane_order_slot
     gsdr::fft::Plan plan{};
     gsdr::fft::Plan4 plan4{};  // four-step plan (variants 20-27, N beyond one workgroup's LDS)
     size_t lds_bytes{0};
@@ -49,7 +50,7 @@ struct gsdr_acq
     float2* d_tw{nullptr};
     float2* d_wipe{nullptr};
     float2* d_code_fft{nullptr};
-    float2* d_code_lane{nullptr};  // the same rows in first-stage lane order (lane_order_slot), variants with lane_nb1 > 0
+    float2* d_code_lane{nullptr};  // the same rows in first-stage lane order (lane_order_slot / lane_pfa), variants with lane_nb1 > 0
     float2* d_code_stage{nullptr};
     uint32_t* d_prn{nullptr};
     uint32_t nprn{0};
@@ -140,7 +141,7 @@ inline int default_pk_variant(uint32_t N)
 {
     switch (N)
         {
-        case 4000: return 99;  // 98 with the twiddle powers and roots from per-workgroup LDS tables: +1.2 % over 98
+        case 4000: return 101;  // 99 with the correlate on the prime-factor 32 x 125 plan: +8 % over 99
         case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
         case 8000: return 61;
         case 2000: return 62;

@@ -438,6 +438,72 @@ constexpr bool lane_order_bijective(int nb1, int r1)
     return true;
 }
 
+// Lane order of a row for the prime-factor first stage (PkPfaPlan4000 of fft_pk.h): natural
+// element i has the coordinates n1 = 21 i mod 32 and n2 = 43 i mod 125 = 5 m + c of
+// i = (125 n1 + 32 n2) mod 4000, and is input m of lane 5 n1 + c.
+constexpr int pfa_lane_order_slot(int i)
+{
+    const int n1 = 21 * i % 32, n2 = 43 * i % 125;
+    return (5 * n1 + n2 % 5) * 25 + n2 / 5;
+}
+// the slot map and the plan's first_index are inverses on [0, 4000): a bijection
+template <class MP>
+constexpr bool pfa_lane_order_bijective()
+{
+    for (int i = 0; i < MP::N; ++i)
+        {
+            const int s = pfa_lane_order_slot(i);
+            if (s < 0 || s >= MP::N || MP::first_index(s / MP::R1, s % MP::R1) != i) return false;
+        }
+    return true;
+}
+// each lane's R1 elements are one residue class mod NB1 (the 25 x 16 x 10 plan's classes, in
+// an order rotated per lane)
+template <class MP>
+constexpr bool pfa_lane_classes()
+{
+    for (int j = 0; j < MP::NB1; ++j)
+        for (int m = 1; m < MP::R1; ++m)
+            if (MP::first_index(j, m) % MP::NB1 != MP::first_index(j, 0) % MP::NB1) return false;
+    return true;
+}
+// the slots follow the data: middle-stage lane j = 125 e + 25 c + k25 reads, as its input m',
+// the first stage's output k25 of lane 5 (2 m' + e) + c, writes only slots that it read, and
+// its output k16 is the last stage's input (e, c) of butterfly (k16, k25)
+template <class MP>
+constexpr bool pfa_slots_chain()
+{
+    for (int j = 0; j < MP::NB2; ++j)
+        {
+            const int e = j / 125, c = j / 25 % 5, k25 = j % 25;
+            for (int r = 0; r < MP::R2; ++r)
+                {
+                    if (MP::middle_slot(j, r) != MP::first_slot(5 * (2 * r + e) + c, k25)) return false;
+                    if (MP::middle_slot(j, r) != MP::last_slot(r, k25, e, c)) return false;
+                    if (MP::middle_slot(j, r) % MP::NB2 != j || MP::middle_slot(j, r) >= MP::N) return false;
+                }
+        }
+    return true;
+}
+// every frequency leaves the last stage once
+template <class MP>
+constexpr bool pfa_outputs_bijective()
+{
+    bool seen[MP::N] = {};
+    for (int j = 0; j < MP::NSL; ++j)
+        for (int r = 0; r < MP::RL; ++r)
+            {
+                const int f = MP::output_index(j % 16, j / 16, r / 5, r % 5);
+                if (f < 0 || f >= MP::N || seen[f]) return false;
+                seen[f] = true;
+            }
+    return true;
+}
+static_assert(pfa_lane_order_bijective<gsdr::pk::PkPfaPlan4000<256>>(), "prime-factor lane order");
+static_assert(pfa_lane_classes<gsdr::pk::PkPfaPlan4000<256>>(), "prime-factor first stage: residue classes mod 160");
+static_assert(pfa_slots_chain<gsdr::pk::PkPfaPlan4000<256>>(), "prime-factor middle stage in place");
+static_assert(pfa_outputs_bijective<gsdr::pk::PkPfaPlan4000<256>>(), "prime-factor output map");
+
 // bytes of the FFT buffer in front of the kernel's statistics scratch
 template <class MP, int CS>
 constexpr size_t pk_fft_bytes()
@@ -464,10 +530,16 @@ constexpr size_t pk_fft_bytes()
 // and the power table read as the ds_read2_b64 pairs the compiler forms (-2 %: the
 // pairs are banked mod 32, where the wrap of k at R1 = 25 makes two lanes of a
 // 16-lane group collide; the conflict cycles nearly doubled).
+//   kTwPfa     the prime-factor plan's (PkPfaPlan4000: no middle-stage twiddles): the 16
+//              roots W_32^k and the 25 roots W_125^k, copied from tw once per workgroup into
+//              the same place; the last stage forms W_125^(c k), c = 2 .. 4, by a chain.
+//              Measured and not kept (profiles/pfa101): the 100 powers W_125^(c k) tabled,
+//              four reads per pass instead of one and three products (-2 %).
 enum TwSrc
 {
     kTwGlobal = 0,
-    kTwLds = 1
+    kTwLds = 1,
+    kTwPfa = 2
 };
 
 // middle-stage table: entry of w^r (1 <= r < r2) for root k of ns2; its elements
@@ -487,6 +559,7 @@ template <class MP, int TW>
 constexpr size_t pk_tw_bytes()
 {
     constexpr int R2 = MP::N / (MP::R1 * MP::RL);
+    if (TW == kTwPfa) return (size_t)(16 + 25) * sizeof(gsdr::pk::c2);
     return (size_t)(tw_mid_elems(TW, R2, MP::R1) + tw_last_elems(TW, MP::NSL)) * sizeof(gsdr::pk::c2);
 }
 template <class MP, int CS, int TW>
@@ -537,6 +610,24 @@ struct TwLds
     __device__ __forceinline__ gsdr::pk::c2 last_root(int k) const { return last[k]; }
 };
 
+// PkPfaPlan4000's twiddle source on the kTwPfa tables: t32[k] = W_32^k, k < 16, then
+// t125[k] = W_125^k, k < 25.  Lanes of equal k25 read one address, the 16 roots of a group
+// lie in 32 consecutive dwords.
+struct TwPfa
+{
+    const gsdr::pk::c2* t32;
+    const gsdr::pk::c2* t125;
+    // once per workgroup, every lane its share, from the handle's table tw[m] = W_4000^m
+    __device__ __forceinline__ static void build(gsdr::pk::c2* t32, const float2* __restrict__ tw, int nt)
+    {
+        gsdr::pk::c2* t125 = t32 + 16;
+        for (int k = (int)threadIdx.x; k < 16; k += nt) t32[k] = gsdr::pk::from(tw[125 * k]);
+        for (int k = (int)threadIdx.x; k < 25; k += nt) t125[k] = gsdr::pk::from(tw[32 * k]);
+    }
+    __device__ __forceinline__ gsdr::pk::c2 root32(int k) const { return t32[k]; }
+    __device__ __forceinline__ gsdr::pk::c2 root125(int k) const { return t125[k]; }
+};
+
 template <class MP, int PG, int WPE, int STAT, int CS, int TW = kTwGlobal>
 __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE))) acq_correlate_pk_kernel(const float2* __restrict__ X,
     const float2* __restrict__ code_fft, RowStat* __restrict__ stats, const float2* __restrict__ tw, uint32_t D,
@@ -544,7 +635,10 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
 {
     static_assert(PG > 0, "PRN group");
     static_assert(CS == kCodeVgpr || CS == kCodeDirect || CS == kCodeLds || CS == kCodeLane, "code source");
-    static_assert(TW == kTwGlobal || TW == kTwLds, "twiddle source");
+    static_assert(TW == kTwGlobal || TW == kTwLds || TW == kTwPfa, "twiddle source");
+    constexpr bool PFA = MP::PRIME_FACTOR;
+    static_assert(PFA == (TW == kTwPfa), "the prime-factor plan and its tables go together");
+    static_assert(!PFA || (CS == kCodeLane && STAT == 2), "prime-factor plan: lane-order code rows, row maximum only");
     constexpr bool PREFETCH = CS == kCodeVgpr;
     constexpr bool LANE = CS == kCodeLane;
     constexpr bool STAGED = CS == kCodeLds || LANE;
@@ -558,7 +652,7 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     static_assert(!TABLES || pk_tw_offset<MP, CS>() % sizeof(gsdr::pk::c2) == 0, "table alignment");
     // four workgroups per CU: 160 KiB / 4
     static_assert(!TABLES || pk_corr_lds_bytes<MP, CS, TW>() <= 40960, "LDS of four workgroups per CU");
-    static_assert(!LANE || (MP::BPT1 == 1 && lane_order_bijective(MP::NB1, MP::R1)), "lane order of the first stage");
+    static_assert(!LANE || (MP::BPT1 == 1 && (PFA || lane_order_bijective(MP::NB1, MP::R1))), "lane order of the first stage");
     // kCodeLds: the last XT of the lane's R1 X values are not resident either: all
     // R1 of them beside the last stage's two passes and the first radix's working
     // set do not fit the 128 VGPRs of four workgroups per CU (the compiler spilled
@@ -598,10 +692,15 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     const int np = (int)min((uint32_t)PG, P - p0);
     // the twiddle source: the tables behind the statistics scratch (built below)
     constexpr int R2 = MP::N / (MP::R1 * MP::RL);
-    using Tws = std::conditional_t<TABLES, TwLds<R2, MP::R1>, gsdr::pk::TwGlobal>;
+    using Tws = std::conditional_t<PFA, TwPfa, std::conditional_t<TABLES, TwLds<R2, MP::R1>, gsdr::pk::TwGlobal>>;
     Tws tws{};
     (void)tws;
-    if constexpr (TABLES)
+    if constexpr (PFA)
+        {
+            tws.t32 = lds + pk_tw_offset<MP, CS>() / sizeof(c2);
+            tws.t125 = tws.t32 + 16;
+        }
+    else if constexpr (TABLES)
         {
             tws.mid = lds + pk_tw_offset<MP, CS>() / sizeof(c2);
             tws.last = tws.mid + tw_mid_elems(TW, R2, MP::R1);
@@ -629,11 +728,27 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
             if (NB1 % NT == 0 || j0 < NB1)
                 {
                     const int jj = min(j, NB1 - 1);
-#pragma unroll
-                    for (int r = 0; r < R1 - XT; ++r)
+                    if constexpr (PFA)
                         {
-                            xr[bb][r] = bload(xrs, jj * 8, r * NB1 * 8);
-                            if constexpr (PREFETCH) cr[bb][r] = bload(crs, jj * 8, r * NB1 * 8);
+                            // the lane's residue class in the plan's rotated order: one wrap per
+                            // load, here only
+                            int i = MP::first_index(jj, 0);
+#pragma unroll
+                            for (int r = 0; r < R1; ++r)
+                                {
+                                    xr[bb][r] = bload(xrs, i * 8, 0);
+                                    i += NB1;
+                                    i = i >= (int)N ? i - (int)N : i;
+                                }
+                        }
+                    else
+                        {
+#pragma unroll
+                            for (int r = 0; r < R1 - XT; ++r)
+                                {
+                                    xr[bb][r] = bload(xrs, jj * 8, r * NB1 * 8);
+                                    if constexpr (PREFETCH) cr[bb][r] = bload(crs, jj * 8, r * NB1 * 8);
+                                }
                         }
                 }
         }
@@ -656,7 +771,9 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
     if constexpr (STAGED)
         {
             stage_code(0);
-            if constexpr (TABLES)
+            if constexpr (PFA)
+                Tws::build(lds + pk_tw_offset<MP, CS>() / sizeof(c2), tw, NT);
+            else if constexpr (TABLES)
                 {
                     // the twiddle tables, once per workgroup, their loads in flight beside the
                     // X row's and code row 0's: every lane copies its share of the last
@@ -908,7 +1025,11 @@ __global__ void __launch_bounds__(PT::NT) acq_argmax_four_kernel(const float2* _
 // (|R|^2 bits, ~index) -- volk_gnsssdr_32f_index_max_32u's strict '>' scan
 // (KERN/32f_index_max_32u.h:446-467) -- then write code_phase and
 // Acq_delay_samples = fmod(indext, samples_per_code) (pcps_acquisition.cc:709).
-template <class MP, int STAT>
+// PEAK: also write the recomputed maximum as the record's peak, ahead of the statistics
+// formed from it -- for a variant whose correlate runs another plan than MP (its row
+// maximum is the same value rounded in another order): the record is then MP's own, bit
+// for bit, whenever the same Doppler row wins.
+template <class MP, int STAT, bool PEAK = false>
 __global__ void __launch_bounds__(MP::NT) acq_argmax_pk_kernel(const float2* __restrict__ X,
     const float2* __restrict__ code_fft, gsdr_acq_result* __restrict__ res, const float2* __restrict__ tw, uint32_t D,
     uint32_t P, float samples_per_code, AcqParams ap)
@@ -949,6 +1070,19 @@ __global__ void __launch_bounds__(MP::NT) acq_argmax_pk_kernel(const float2* __r
             const uint32_t idx = 0xffffffffu - (uint32_t)(key & 0xffffffffu);
             res[bp].code_phase = idx;
             res[bp].acq_delay_samples = (double)fmodf((float)idx, samples_per_code);
+            if constexpr (PEAK)
+                {
+                    const float peak = __uint_as_float((uint32_t)(key >> 32));
+                    res[bp].peak = peak;
+                    // step two's statistic, which acq_reduce_kernel formed from the row maximum
+                    // (the first step's is formed below, the peak ratio's by the second-peak pass)
+                    if (ap.cfar && ap.step_two)
+                        {
+                            const float stat = peak / res[bp].input_power;
+                            res[bp].test_statistic = stat;
+                            res[bp].positive = stat > ap.threshold ? 1 : 0;
+                        }
+                }
         }
     if constexpr (STAT >= 2)
         {

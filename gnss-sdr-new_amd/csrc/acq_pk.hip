@@ -48,13 +48,25 @@ using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // the last stage's roots, built once per workgroup, read ahead of each stage's barrier --
 // no global load left in a transform but the code-row copies, 28 packed products fewer per
 // wave; 126 VGPRs, no scratch, occupancy 4, 39,096 B of LDS): +1.2 % over 98 on the C2
-// bench, bit-identical results; 98 stays as its A/B partner.
-template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr, int TW_ = kTwGlobal>
+// bench, bit-identical results; 98 stays as its A/B partner.  101 is 99 with the correlate's
+// transform as the prime-factor 32 x 125 plan (PkPfaPlan4000 of fft_pk.h: the same radices 25,
+// 16, 10, no twiddles between the first two stages, the middle stage in place -- 4 barriers per
+// transform --, a 2 x 5 last butterfly with 13 twiddle products instead of 21, the roots from
+// two small LDS tables, kTwPfa; 122 VGPRs, no scratch, occupancy 4, 33,224 B of LDS).  Forward
+// and argmax passes stay on the Stockham plan, and the argmax pass writes the record's peak, so
+// the records are variant 70's bit for bit wherever the same Doppler row wins; the row maxima
+// differ from 70's by f32 rounding order (tests/test_gpu_acq_pk_prime_factor.py).  +8 % over 99
+// on the C2 bench; 99 stays as its A/B partner.  Measured on the way and not kept
+// (profiles/pfa101): the powers W_125^(c k) read from a table instead of chained (-2 %).
+template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr, int TW_ = kTwGlobal, class CP = MP>
 struct PkVariant
 {
     static constexpr int id = ID, PG = PG_, WPE = WPE_, STAT = ST, CS = CS_, TW = TW_;
     using type = MP;
     using Reg = REG;
+    using Corr = CP;  // the plan acq_correlate_pk_kernel runs (forward and argmax: type)
+    // another plan's row maximum selects the row; the record's peak is the argmax pass's
+    static constexpr bool PEAK = !std::is_same<CP, MP>::value;
 };
 using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1>,
     PkVariant<62, PkPlan<256, true, 20, 10, 10>, 1, 1, 1>,
@@ -63,7 +75,8 @@ using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1
     PkVariant<70, PkPlan<256, 1, 25, 16, 10>, 1, 1, 2>,
     PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>,
     PkVariant<98, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane>,
-    PkVariant<99, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwLds>>;
+    PkVariant<99, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwLds>,
+    PkVariant<101, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwPfa, gsdr::pk::PkPfaPlan4000<256>>>;
 
 // f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
 // internal error in a launch: setup accepted the handle's id).
@@ -96,7 +109,7 @@ int launch_corr_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, hipStre
         else
             {
                 const uint32_t groups = (v.nprn + V::PG - 1) / V::PG;
-                hipLaunchKernelGGL((acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS, V::TW>), dim3(nblocks * v.D * groups),
+                hipLaunchKernelGGL((acq_correlate_pk_kernel<typename V::Corr, V::PG, V::WPE, V::STAT, V::CS, V::TW>), dim3(nblocks * v.D * groups),
                     dim3(M::NT), a->corr_lds_bytes, s, a->d_X, V::CS == kCodeLane ? v.code_lane : v.code_fft, a->d_stats, a->d_tw, v.D, v.nprn, nblocks,
                     v.xm);
             }
@@ -110,7 +123,7 @@ int launch_argmax_variant(gsdr_acq* a, const AcqView& v, uint32_t nblocks, gsdr_
     return with_pk_variant(a->corr_variant, [&](auto e) {
         using V = decltype(e);
         using M = typename V::type;
-        hipLaunchKernelGGL((acq_argmax_pk_kernel<M, V::STAT>), dim3(nblocks * v.nprn), dim3(M::NT), a->corr_lds_bytes,
+        hipLaunchKernelGGL((acq_argmax_pk_kernel<M, V::STAT, V::PEAK>), dim3(nblocks * v.nprn), dim3(M::NT), a->corr_lds_bytes,
             s, a->d_X, v.code_fft, res, a->d_tw, v.D, v.nprn, a->conf.samples_per_code, params_of(a, v));
         GSDR_HIP(hipGetLastError());
         return GSDR_OK;
@@ -147,9 +160,11 @@ int setup_corr_variant(gsdr_acq* a, int id)
         // the correlate's FFT buffer (padded for kCodeLds), two sets of per-wave row statistics and
         // the variant's twiddle tables; the argmax pass, scratch right after its N c2, fits in the
         // same allocation
-        a->corr_lds_bytes = pk_corr_lds_bytes<M, V::CS, V::TW>();
-        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<M, V::PG, V::WPE, V::STAT, V::CS, V::TW>, a->corr_lds_bytes);
-        rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT>, a->corr_lds_bytes);
+        using C = typename V::Corr;
+        static_assert(C::N == M::N && C::NT == M::NT && C::lds_bytes() >= M::lds_bytes(), "one size, one workgroup, one allocation");
+        a->corr_lds_bytes = pk_corr_lds_bytes<C, V::CS, V::TW>();
+        int rc = set_max_lds((const void*)acq_correlate_pk_kernel<C, V::PG, V::WPE, V::STAT, V::CS, V::TW>, a->corr_lds_bytes);
+        rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT, V::PEAK>, a->corr_lds_bytes);
         for (int it : kItemTypes)
             rc |= with_item_type(it, [&](auto t) {
                 return set_max_lds((const void*)acq_forward_pk_kernel<M, decltype(t)::value>, M::lds_bytes());
@@ -158,8 +173,9 @@ int setup_corr_variant(gsdr_acq* a, int id)
             rc |= set_max_lds((const void*)acq_correlate_reg_kernel<typename V::Reg>, V::Reg::lds_bytes());
         if (rc != GSDR_OK) return GSDR_E_DEVICE;
         a->corr_variant = V::id;
-        a->lane_nb1 = V::CS == kCodeLane ? M::NB1 : 0;
-        a->lane_r1 = V::CS == kCodeLane ? M::R1 : 0;
+        a->lane_nb1 = V::CS == kCodeLane ? C::NB1 : 0;
+        a->lane_r1 = V::CS == kCodeLane ? C::R1 : 0;
+        a->lane_pfa = V::CS == kCodeLane && C::PRIME_FACTOR ? 1 : 0;
         a->corr_stat = V::STAT;
         return GSDR_OK;
     }, GSDR_OK);

@@ -516,6 +516,7 @@ struct PkPlan
     static constexpr bool TWP = TWP_ != 0;
     static constexpr int N = (Rs * ...);
     static constexpr int nstages = sizeof...(Rs);
+    static constexpr bool PRIME_FACTOR = false;  // (PkPfaPlan4000 below: first-stage inputs by its own index map)
     static constexpr int R1 = fft::FirstRadix<Rs...>::value;
     static constexpr int BPT1 = fft::bpt_for(R1);
     static constexpr int NB1 = N / R1;
@@ -536,6 +537,172 @@ struct PkPlan
         Pre pre = Pre{}, Mid mid = Mid{}, Tws tws = Tws{})
     {
         stages<NT, N, 1, TWP, true, ORD, SKIPW, Rs...>(lds, tw, load, store, hook, pre, mid, tws);
+    }
+};
+
+// ---- prime-factor plan, N = 4000 = 32 x 125 ----
+// gcd(32, 125) = 1, so by Good-Thomas the 4000-point DFT is a true 32 x 125 two-
+// dimensional DFT, no twiddle between the dimensions: with i = (125 n1 + 32 n2) mod N and
+// k = (2625 k1 + 1376 k2) mod N, W_N^(i k) = W_32^(n1 k1) W_125^(n2 k2).  The stages keep
+// PkPlan<256,1,25,16,10>'s radices, read as 125 = 25 x 5 (n2 = 5 m + c, k2 = k25 + 25 k5)
+// and 32 = 16 x 2 (n1 = 2 m' + e, k1 = k16 + 16 k2'):
+//   A  radix 25 over m, 160 butterflies, lane t = 5 n1 + c; output k25 to slot
+//      25 t + k25 = 125 n1 + 25 c + k25 (first_index / first_slot: the lane-order image);
+//   B  radix 16 over m', 250 butterflies, no twiddles: lane j = 125 e + 25 c + k25 reads
+//      slots j + 250 m' and writes output k16 to j + 250 k16 -- the slots it alone read, and
+//      a wave's LDS operations execute in order, so no barrier between reads and writes;
+//   C  400 butterflies of 2 x 5 points in two passes, lane numbering k16 fastest (k16 =
+//      j mod 16, k25 = j div 16: both passes of a lane share k16, and the 32 lanes of a
+//      ds_read_b64 group touch 32 different slots mod 32); input (e, c) at slot
+//      250 k16 + k25 + 125 e + 25 c.  u[1][c] *= W_32^k16 (one root), Dft<2> over e, both
+//      halves times W_125^(c k25), c = 1 .. 4, Dft<5> over c: a prime-factor butterfly, no
+//      internal W_10 twiddles.  Output (k2', k5) is frequency output_index().
+// Against the 25 x 16 x 10 Stockham plan: no middle-stage twiddles, 13 twiddle products in
+// a last-stage butterfly instead of 17 + the 4 of DftCT<2,5>, one barrier fewer.  The
+// outputs come in an order of their own, for order-free statistics (ORD = false) only.
+// run() has PkPlan::run's interface; load(0, r, i) gets the natural index
+// i = first_index(j, r), and tws is a source of the two root tables:
+//   tws.root32(k)            W_32^k, k < 16
+//   tws.root125(k)           W_125^k, k < 25; the stage forms W_125^(c k), c = 2 .. 4, by a
+//                            three-product chain (the powers read from a table instead:
+//                            measured, -2 %, profiles/pfa101)
+// both read beside the last stage's inputs, ahead of its barrier.
+template <int NT_>
+struct PkPfaPlan4000
+{
+    static_assert(NT_ == 256, "160 / 250 / 2 x 200 butterflies on 256 lanes");
+    static constexpr int NT = NT_;
+    static constexpr bool TWP = true;
+    static constexpr int N = 4000;
+    static constexpr int nstages = 3;
+    static constexpr bool PRIME_FACTOR = true;
+    static constexpr int R1 = 25, BPT1 = 1, NB1 = 160;
+    static constexpr int R2 = 16, NB2 = 250;
+    static constexpr int RL = 10, BPTL = 2, NSL = 400, NSLOTS = RL * BPTL;
+    static constexpr size_t lds_bytes() { return (size_t)N * sizeof(c2); }
+    // stage A: natural index of input m of lane j = 5 n1 + c, and the slot of its output k25
+    static constexpr int first_index(int j, int m) { return (125 * (j / 5) + 32 * (j % 5) + 160 * m) % N; }
+    static constexpr int first_slot(int j, int k25) { return 25 * j + k25; }
+    // stage B: slot of input m' and of output k16 of lane j
+    static constexpr int middle_slot(int j, int r) { return j + NB2 * r; }
+    // stage C: slot of input (e, c) of butterfly (k16, k25); frequency of its output (k2', k5)
+    static constexpr int last_slot(int k16, int k25, int e, int c) { return 250 * k16 + k25 + 125 * e + 25 * c; }
+    static constexpr int output_index(int k16, int k25, int k2, int k5)
+    {
+        return (2625 * (k16 + 16 * k2) + 1376 * (k25 + 25 * k5)) % N;
+    }
+
+    template <bool ORD = false, bool SKIPW = false, class Load, class Store, class Hook, class Pre, class Mid, class Tws>
+    __device__ __forceinline__ static void run(c2* lds, const float2* __restrict__, Load load, Store store, Hook hook, Pre,
+        Mid mid, Tws tws)
+    {
+        static_assert(!ORD, "the outputs are not visited in index order");
+        static_assert(std::is_same<Pre, NoHook>::value, "no pre() hook: the first stage takes the ordinary write path");
+        const int t = (int)threadIdx.x;
+        // ---- A
+        {
+            c2 v[R1];
+            const int jj = min(t, NB1 - 1);
+            // SKIPW: as stage() -- a wave without a butterfly skips the loads
+            if (!SKIPW || __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) < NB1)
+                {
+#pragma unroll
+                    for (int r = 0; r < R1; ++r) v[r] = load(0, r, first_index(jj, r));
+                }
+            hook();
+            if (t < NB1)
+                {
+                    Dft<R1>::run(v);
+#pragma unroll
+                    for (int r = 0; r < R1; ++r) lds[first_slot(t, r)] = v[r];
+                }
+            __syncthreads();
+        }
+        // ---- B (in place; the idle lanes read a clamped index and write nothing)
+        {
+            c2 v[R2];
+            const int jj = min(t, NB2 - 1);
+#pragma unroll
+            for (int r = 0; r < R2; ++r) v[r] = lds[middle_slot(jj, r)];
+            if (t < NB2)
+                {
+                    Dft<R2>::run(v);
+#pragma unroll
+                    for (int r = 0; r < R2; ++r) lds[middle_slot(t, r)] = v[r];
+                }
+            __syncthreads();
+        }
+        // ---- C
+        {
+            c2 v[BPTL][RL];
+            c2 w125[BPTL][4];
+            const int k16 = t & 15, k25 = t >> 4;      // second pass: k25 + 16, lanes below 144
+            const int k25b = min(k25 + 16, 24);
+            const c2 w32 = tws.root32(k16);
+            w125[0][0] = tws.root125(k25);
+            w125[1][0] = tws.root125(k25b);
+            // The inputs as single ds_read_b64 (banked mod 64: conflict-free in this numbering; the
+            // ds_read2_b64 pairs the compiler would form are banked mod 32, two-way conflicts).  The
+            // compiler does not count these reads, so the stage waits for them itself, as TwLds::middle
+            // does: the second pass's wait stands in the statement of its reads, the first pass's
+            // registers are named behind the wait, ahead of their first use.
+            const unsigned a0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(lds + last_slot(k16, k25, 0, 0));
+            const unsigned a1 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)(lds + last_slot(k16, k25b, 0, 0));
+            static_assert(last_slot(0, 0, 0, 1) * 8 == 200 && last_slot(0, 0, 1, 0) * 8 == 1000, "the offsets below");
+#define GSDR_PFA_READS                                                                                           \
+    "ds_read_b64 %0, %10\n\tds_read_b64 %1, %10 offset:200\n\tds_read_b64 %2, %10 offset:400\n\t"              \
+    "ds_read_b64 %3, %10 offset:600\n\tds_read_b64 %4, %10 offset:800\n\tds_read_b64 %5, %10 offset:1000\n\t"  \
+    "ds_read_b64 %6, %10 offset:1200\n\tds_read_b64 %7, %10 offset:1400\n\tds_read_b64 %8, %10 offset:1600\n\t" \
+    "ds_read_b64 %9, %10 offset:1800"
+#define GSDR_PFA_REGS(B)                                                                                         \
+    "=&v"(v[B][0]), "=&v"(v[B][1]), "=&v"(v[B][2]), "=&v"(v[B][3]), "=&v"(v[B][4]), "=&v"(v[B][5]), "=&v"(v[B][6]),  \
+        "=&v"(v[B][7]), "=&v"(v[B][8]), "=&v"(v[B][9])
+            asm volatile(GSDR_PFA_READS : GSDR_PFA_REGS(0) : "v"(a0) : "memory");
+            // (a wave without a butterfly in the second pass skips its reads)
+            if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u)) < NSL - NT)
+                asm volatile(GSDR_PFA_READS "\n\ts_waitcnt lgkmcnt(0)" : GSDR_PFA_REGS(1) : "v"(a1) : "memory");
+            else
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#undef GSDR_PFA_READS
+#undef GSDR_PFA_REGS
+#pragma unroll
+            for (int r = 0; r < RL; ++r) asm volatile("" : "+v"(v[0][r]));
+            __syncthreads();
+            // every lane's inputs are in registers: the buffer is dead until the next first stage
+            mid();
+#pragma unroll
+            for (int b = 0; b < BPTL; ++b)
+                {
+                    if (b == 0 || t < NSL - NT)
+                        {
+                            c2* u = v[b];  // u[5 e + c]
+#pragma unroll
+                            for (int c = 0; c < 5; ++c) u[5 + c] = mul(u[5 + c], w32);
+#pragma unroll
+                            for (int c = 0; c < 5; ++c)
+                                {
+                                    const c2 p = u[c], q = u[5 + c];
+                                    u[c] = p + q;
+                                    u[5 + c] = p - q;
+                                }
+                            c2* w = w125[b];
+                            w[1] = mul(w[0], w[0]);
+                            w[2] = mul(w[1], w[0]);
+                            w[3] = mul(w[2], w[0]);
+#pragma unroll
+                            for (int c = 1; c < 5; ++c)
+                                {
+                                    u[c] = mul(u[c], w[c - 1]);
+                                    u[5 + c] = mul(u[5 + c], w[c - 1]);
+                                }
+                            Dft<5>::run(u);
+                            Dft<5>::run(u + 5);
+                            const int kk = k25 + 16 * b;
+#pragma unroll
+                            for (int r = 0; r < RL; ++r) store(output_index(k16, kk, r / 5, r % 5), u[r], r * BPTL + b);
+                        }
+                }
+        }
     }
 };
 

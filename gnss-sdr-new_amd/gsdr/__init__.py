@@ -51,6 +51,7 @@ EXPORTED = [
     "gsdr_stream_wait_landed",
     "gsdr_stream_read", "gsdr_firdes_low_pass", "gsdr_acq_resampler_plan", "gsdr_decim_create", "gsdr_decim_destroy",
     "gsdr_decim_output", "gsdr_decim_advance", "gsdr_acq_get_plan", "gsdr_acq_get_split",
+    "gsdr_acq_dump_row_maxima",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -243,6 +244,8 @@ def load():
     L.gsdr_acq_run_device.argtypes = [P, P, U32, U64, U64, P, P]
     L.gsdr_acq_dump_grid.argtypes = [P, P, U32, P]
     L.gsdr_acq_dump_grid_step_two.argtypes = [P, P, U32, ctypes.c_float, P]
+    if hasattr(L, "gsdr_acq_dump_row_maxima"):  # (an earlier build selected by GSDR_LIB for an A/B lacks it)
+        L.gsdr_acq_dump_row_maxima.argtypes = [P, P, P]
     L.gsdr_acq_read_profile_intervals.argtypes = [P, P, ctypes.c_int, P, P, U32, P]
     L.gsdr_acq_set_wipeoff.argtypes = [P, ctypes.c_int]
     L.gsdr_acq_get_spectrum_reuse.argtypes = [P, P, P]
@@ -563,6 +566,14 @@ class Acquisition:
         g = np.zeros((self.num_doppler_bins, self.fft_size), np.float32)
         _check(load().gsdr_acq_dump_grid(self._h, _ptr(iq), int(prn_slot), _ptr(g)))
         return g
+
+    def dump_row_maxima(self, iq):
+        """The row maxima [num_doppler_bins, nprn] of one block, as the handle's packed
+        correlate variant computes them (gsdr_acq_dump_row_maxima)."""
+        iq = self._items(iq)
+        m = np.zeros((self.num_doppler_bins, self.nprn), np.float32)
+        _check(load().gsdr_acq_dump_row_maxima(self._h, _ptr(iq), _ptr(m)))
+        return m
 
     def dump_grid_step_two(self, iq, prn_slot, doppler_center_hz):
         """The make_two_steps narrow grid of one block (set_step_two first)."""

@@ -360,6 +360,14 @@ int gsdr_acq_collect(gsdr_acq* acq, gsdr_acq_result* out_host, uint32_t* nblocks
  * |R|^2 grid of PRN slot `prn_slot` for one host block into grid_host
  * (D rows of fft_size floats, Doppler-major).  Synchronous. */
 int gsdr_acq_dump_grid(gsdr_acq* acq, const void* iq_host, uint32_t prn_slot, float* grid_host);
+/* The correlate pass's own product for one host block: the forward spectra, then the
+ * handle's packed correlate variant (the kernel a run launches, on the active PRN
+ * slots), then its row maxima max_n |R_{d,p}[n]|^2 into out_host, D rows of nprn
+ * floats (Doppler-major).  A run shows these only through the Doppler row that wins;
+ * gsdr_acq_dump_grid recomputes the rows with another kernel.  GSDR_E_UNSUPPORTED for
+ * a handle without a packed variant (other FFT sizes, dwells, bit transition).
+ * Synchronous. */
+int gsdr_acq_dump_row_maxima(gsdr_acq* acq, const void* iq_host, float* out_host);
 /* The narrow grid of make_two_steps for the same dump (d_narrow_grid,
  * pcps_acquisition.cc:743-746, written by dump_results :493-506): the |R|^2 grid of
  * PRN slot prn_slot over the num_doppler_bins_step2 rows centred on
