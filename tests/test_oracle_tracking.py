@@ -13,6 +13,8 @@ import pytest
 from gsdr import synth
 from oracle import trk
 
+import trk_checks as tc
+
 STEP = np.array([0.0, 0.0, 1.0, 0.0, 0.0, 0.0], np.float32)
 
 
@@ -94,6 +96,71 @@ def test_channel_loses_lock_on_noise():
     recs, _ = ch.run(iq, 0, first, 4000)
     assert recs["flags"][-1] & trk.F_LOSS_OF_LOCK
     assert ch.state == 0
+
+
+_SCENARIOS = ([("option", "signal", ov, tc.N_CALLS, 1158, None) for ov in tc.OPTION_CASES]
+              + [("pull_in", "signal_long", tc.PULL_IN_CASE["overrides"], tc.PULL_IN_CASE["calls"],
+                  tc.PULL_IN_CASE["sync_call"], None)]
+              + [("loss", name, ov, 4000, None, (call, state, ext)) for name, ov, call, state, ext in tc.LOSS_CASES])
+
+
+@pytest.mark.parametrize("kind,name,overrides,calls,sync_call,loss", _SCENARIOS,
+                         ids=["%s:%s:%s" % (s[0], s[1], tc.case_id(s[2])) for s in _SCENARIOS])
+def test_loop_option_scenarios(kind, name, overrides, calls, sync_call, loss):
+    """The scenarios of trk_checks (loop options, the longer pull-in, the losses the
+    detectors reach themselves) on the oracle alone: what the GPU tests of
+    test_gpu_trk_loop_options.py take for granted about these inputs.  Option and
+    pull-in cases stay locked for all their calls, synchronise once at the stated
+    call and end in state 4; a loss case has one loss-of-lock record, the last one,
+    at the stated call and state, and leaves the channel in standby."""
+    recs, _, ch = tc.oracle_free_run(name, overrides, calls)
+    lost = np.nonzero(recs["flags"] & trk.F_LOSS_OF_LOCK)[0]
+    sync = np.nonzero(recs["flags"] & trk.F_BIT_SYNC)[0]
+    if loss is None:
+        assert len(recs) == calls and len(lost) == 0
+        assert list(sync) == [sync_call] and recs["state"][-1] == 4 and ch.state == 4
+        assert np.all(recs["state"][:sync_call + 1] == 2) and np.all(recs["state"][sync_call + 1:] == 4)
+        if kind == "option":  # all eleven end near 1231.6 Hz and 45.5 dB-Hz (cn0_samples = 7: 46.5)
+            assert abs(recs["carrier_doppler_hz"][-1] - 1231.6) < 0.5
+            assert abs(recs["cn0_db_hz"][-1] - 45.5) < 1.5
+    else:
+        call, state, through_ext = loss
+        assert list(lost) == [call] and len(recs) == call + 1
+        assert recs["state"][-1] == state and ch.state == 0
+        assert (3 in recs["state"]) == through_ext
+        assert len(sync) == (1 if state == 4 else 0)
+
+
+def test_order3_code_filter_float_drift():
+    """Where trk_checks.DLL3_BOUNDS come from: on the free-running oracle with
+    dll_filter_order = 3, lf3_apply in float is the oracle's code filter bit for bit,
+    and the same recursion in float64 on the same inputs lies the recorded distances
+    away (the double integrator keeps every rounding of its input sum)."""
+    recs, _, _ = tc.oracle_free_run("signal", dict(dll_filter_order=3), tc.N_CALLS)
+    model, d_filt, d_rem = tc.lf3_float_vs_f64(recs)
+    assert model == 0.0
+    assert d_filt == pytest.approx(tc.DLL3_FLOAT_VS_F64["code_freq_chips"], rel=1e-3)
+    assert d_rem == pytest.approx(tc.DLL3_FLOAT_VS_F64["rem_code_phase_samples"], rel=1e-3)
+    assert tc.DLL3_BOUNDS == {f: 2.0 * d for f, d in tc.DLL3_FLOAT_VS_F64.items()}
+
+
+def test_high_dynamics_rate_float_sensitivity():
+    """Where trk_checks.HD_RESTART_BOUNDS come from: on the free-running oracle of the
+    restarted high_dyn run, pll3_apply in float and hd_carrier_rates are the oracle's
+    Doppler and rate steps bit for bit, and the rates that follow from the same
+    carrier filter in float64 lie the recorded distances away."""
+    iq, stamp = tc.restart_input(False)
+    conf = tc.scenario_conf(dict(max_carrier_lock_fail=50, **tc.RESTART_HD))
+    delay, dop = tc._acq(tc.RESTART_SAT, tc.FS)
+    ch = trk.Channel(conf[0:1].view(trk.TRK_CONF_DTYPE))
+    first = ch.start(synth.gps_ca_chips(tc.RESTART_SAT.prn), delay, dop, stamp, stamp + tc.NITEMS)
+    recs, _ = ch.run(iq, 0, first, tc.RESTART_CALLS + 1)
+    assert len(recs) == tc.RESTART_CALLS + 1 and np.all(recs["state"] == 2)
+    model_dop, model_rates, d_carr, d_code = tc.hd_rates_float_vs_f64(recs, dop, tc.RESTART_HD["smoother_length"])
+    assert model_dop == 0.0 and model_rates == 0
+    assert d_carr == pytest.approx(tc.HD_RESTART_FLOAT_VS_F64["carrier_rate"], rel=1e-3)
+    assert d_code == pytest.approx(tc.HD_RESTART_FLOAT_VS_F64["code_rate"], rel=1e-3)
+    assert tc.HD_RESTART_BOUNDS == {f: 2.0 * d for f, d in tc.HD_RESTART_FLOAT_VS_F64.items()}
 
 
 @pytest.mark.parametrize("at,cn0_fill", [(10, False), (300, True), (1300, True)])
