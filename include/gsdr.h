@@ -466,7 +466,7 @@ int gsdr_corr_set_resampler_assoc(gsdr_corr* corr, int assoc);
 
 /* Synchronous drop-in for one channel: Carrier_wipeoff_multicorrelator_resampler
  * (7-argument form) on host samples; writes n_taps complex<float> to corr_out_host.
- * item_type selects gr_complex or cshort input. */
+ * item_type selects gr_complex, cshort or ibyte input (GSDR_ITEM_*). */
 int gsdr_corr_run(gsdr_corr* corr, int channel, const void* sig_in_host, int item_type, float rem_carr_phase_rad,
     float carr_phase_step_rad, float carr_phase_rate_step_rad, float rem_code_phase_chips,
     float code_phase_step_chips, float code_phase_rate_step_chips, int signal_length_samples, float* corr_out_host);

@@ -45,6 +45,8 @@ def lib():
         L.orc_multicorrelator_real_codes.argtypes = [_p, _p, _p, _u, _p, _i, _f, _f, _f, _f, _f, _f, _u, _i, _i]
         L.orc_multicorrelator_complex_codes.argtypes = [_p, _p, _p, _u, _p, _i, _f, _f, _f, _f, _u, _i]
         L.orc_multicorrelator_real_codes_exact.argtypes = [_p, _p, _p, _u, _p, _i, _f, _f, _f, _f, _u, _i]
+        L.orc_multicorrelator_complex_codes_exact.argtypes = [_p, _p, _p, _u, _p, _i, _f, _f, _f, _f, _u, _i]
+        L.orc_multicorrelator_real_codes_hd_exact.argtypes = [_p, _p, _p, _u, _p, _i, _f, _f, _f, _f, _f, _f, _u]
         _lib = L
     return _lib
 
@@ -166,4 +168,28 @@ def multicorrelator_real_codes_exact(sig, code, shifts, rem_carr, carr_step, rem
     out = np.empty(2 * len(shifts), np.float64)
     lib().orc_multicorrelator_real_codes_exact(_ptr(out), _ptr(sig), _ptr(code), len(code), _ptr(shifts),
                                                len(shifts), rem_carr, carr_step, rem_code, code_step, N, assoc)
+    return out[0::2] + 1j * out[1::2]
+
+
+def multicorrelator_complex_codes_exact(sig, code, shifts, rem_carr, carr_step, rem_code, code_step, N, assoc=1):
+    """fp64 evaluation of multicorrelator_complex_codes' phase model and indices."""
+    sig = _c(sig, np.complex64)
+    code = _c(code, np.complex64)
+    shifts = _c(shifts, np.float32)
+    out = np.empty(2 * len(shifts), np.float64)
+    lib().orc_multicorrelator_complex_codes_exact(_ptr(out), _ptr(sig), _ptr(code), len(code), _ptr(shifts),
+                                                  len(shifts), rem_carr, carr_step, rem_code, code_step, N, assoc)
+    return out[0::2] + 1j * out[1::2]
+
+
+def multicorrelator_real_codes_hd_exact(sig, code, shifts, rem_carr, carr_step, rem_code, code_step, N,
+                                        carr_rate=0.0, code_rate=0.0):
+    """fp64 evaluation of multicorrelator_real_codes(high_dyn=True)."""
+    sig = _c(sig, np.complex64)
+    code = _c(code, np.float32)
+    shifts = _c(shifts, np.float32)
+    out = np.empty(2 * len(shifts), np.float64)
+    lib().orc_multicorrelator_real_codes_hd_exact(_ptr(out), _ptr(sig), _ptr(code), len(code), _ptr(shifts),
+                                                  len(shifts), rem_carr, carr_step, carr_rate, rem_code, code_step,
+                                                  code_rate, N)
     return out[0::2] + 1j * out[1::2]

@@ -505,3 +505,64 @@ void orc_multicorrelator_real_codes_exact(double* out, const float* sig, const f
                 }
         }
 }
+
+/* Exact companion of orc_multicorrelator_complex_codes: the same construction
+ * with the complex resampler's indices (orc_resampler_32fc_xn) and the complex
+ * product of KERN/32fc_x2_rotator_dot_prod_32fc_xn.h in double. */
+void orc_multicorrelator_complex_codes_exact(double* out, const float* sig, const float* code, unsigned int L,
+    const float* shifts, int K, float rem_carr, float carr_step, float rem_code, float code_step,
+    unsigned int N, int assoc)
+{
+    const cf32* cc = (const cf32*)code;
+    float complex inc = cexpf(0.0f + I * (-carr_step));
+    double th = atan2((double)cimagf(inc), (double)crealf(inc));
+    double ps = atan2((double)(-sinf(rem_carr)), (double)cosf(rem_carr));
+    for (int k = 0; k < 2 * K; k++) out[k] = 0.0;
+    for (unsigned int n = 0; n < N; n++)
+        {
+            double phi = ps + th * (double)n;
+            double c = cos(phi), s = sin(phi);
+            double xr = sig[2 * n], xi = sig[2 * n + 1];
+            double tr = xr * c - xi * s, ti = xr * s + xi * c;
+            for (int k = 0; k < K; k++)
+                {
+                    cf32 a = cc[code_index(code_step, shifts[k], rem_code, n, L, assoc)];
+                    out[2 * k] += tr * (double)a.re - ti * (double)a.im;
+                    out[2 * k + 1] += tr * (double)a.im + ti * (double)a.re;
+                }
+        }
+}
+
+/* Exact companion of orc_multicorrelator_real_codes(high_dyn = 1): the replicas of
+ * the high-dynamics resampler (orc_high_dyn_resampler_32f_xn) and the phase
+ * orc_high_dyn_rotator_dot_prod_32fc_32f_xn documents,
+ *   phi_0 = psi0,  phi_n = psi0 + theta n + theta_rate (n-1)^2  for n >= 1,
+ * with theta_rate the angle of the float-rounded exp(-j carr_rate). */
+void orc_multicorrelator_real_codes_hd_exact(double* out, const float* sig, const float* code, unsigned int L,
+    const float* shifts, int K, float rem_carr, float carr_step, float carr_rate, float rem_code,
+    float code_step, float code_rate, unsigned int N)
+{
+    float* rs = (float*)malloc((size_t)K * (N ? N : 1) * sizeof(float));
+    if (N) orc_high_dyn_resampler_32f_xn(rs, code, rem_code, code_step, code_rate, shifts, L, K, N);
+    float complex inc = cexpf(0.0f + I * (-carr_step));
+    float complex rate = cexpf(0.0f + I * (-carr_rate));
+    double th = atan2((double)cimagf(inc), (double)crealf(inc));
+    double thr = atan2((double)cimagf(rate), (double)crealf(rate));
+    double ps = atan2((double)(-sinf(rem_carr)), (double)cosf(rem_carr));
+    for (int k = 0; k < 2 * K; k++) out[k] = 0.0;
+    for (unsigned int n = 0; n < N; n++)
+        {
+            double phi = ps + th * (double)n;
+            if (n > 0) phi += thr * (double)(n - 1) * (double)(n - 1);
+            double c = cos(phi), s = sin(phi);
+            double xr = sig[2 * n], xi = sig[2 * n + 1];
+            double tr = xr * c - xi * s, ti = xr * s + xi * c;
+            for (int k = 0; k < K; k++)
+                {
+                    double a = rs[(size_t)k * N + n];
+                    out[2 * k] += tr * a;
+                    out[2 * k + 1] += ti * a;
+                }
+        }
+    free(rs);
+}
