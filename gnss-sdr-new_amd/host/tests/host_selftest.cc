@@ -604,8 +604,7 @@ void test_acquisition_dwells(const std::vector<std::complex<float>>& capture)
             EXPECT(r.num_dwells == 2, "one-shot attempt reports its last dwell");
             EXPECT(std::abs(r.test_statistic - stat_block) <= 1e-5F * std::abs(r.test_statistic),
                 "per-call dwell statistic == one-shot dwell statistic");
-            EXPECT(std::abs(gs.Acq_delay_samples - r.acq_delay_samples) < 0.5 &&
-                       std::abs(gs.Acq_doppler_hz - r.doppler_hz) < 0.5,
+            EXPECT(gs.Acq_delay_samples == r.acq_delay_samples && gs.Acq_doppler_hz == static_cast<double>(r.doppler_hz),
                 "per-call dwell cell == one-shot dwell cell");
             std::printf("dwells (pfa %s): per-call stat %.5f, one-shot %.5f, delay %.0f doppler %.0f\n", pfa, stat_block,
                 r.test_statistic, gs.Acq_delay_samples, gs.Acq_doppler_hz);
@@ -617,6 +616,45 @@ void test_acquisition_dwells(const std::vector<std::complex<float>>& capture)
             run_acquisition(acq.get_block(), capture.data(), capture.size(), 1000, &ev);
             EXPECT(ev == 1 && acq.get_block()->num_noncoherent_integrations() == 0, "positive first dwell resets the counter");
             EXPECT(std::abs(gs.Acq_delay_samples - 524.0) < 1.0, "PRN 1 at 524 samples");
+        }
+}
+
+// set_doppler_center (assisted acquisition, acquisition_interface.h:59): with
+// doppler_max 1000 the grid centred on zero ends at 750 Hz and PRN 1 of the capture
+// (1680 Hz) lies outside it; centred on 1500 Hz the rows run 500 .. 2250 Hz.  The centre
+// reaches the engine through init() (set before it) and through gsdr_acq_set_doppler on
+// the live engine (set after it): either way the block reports a row of the moved grid.
+void test_acquisition_doppler_center(const std::vector<std::complex<float>>& capture)
+{
+    for (const bool before_init : {true, false})
+        {
+            InMemoryConfiguration config = gps_acq_config("Acquisition_1C.pfa", "0.01");
+            config.set_property("Acquisition_1C.doppler_max", "1000");
+            Gnss_Synchro gs{};
+            gs.System = 'G';
+            gs.Signal[0] = '1';
+            gs.Signal[1] = 'C';
+            gs.PRN = 1;
+            GpsL1CaPcpsAcquisitionMI355X acq(&config, "Acquisition_1C", 1, 0);
+            int ev = 0;
+            acq.get_block()->set_event_handler([&](int e) { ev = e; });
+            acq.set_gnss_synchro(&gs);
+            acq.set_local_code();
+            if (before_init) acq.set_doppler_center(1500);
+            acq.set_state(1);
+            acq.init();
+            if (!before_init) acq.set_doppler_center(1500);
+            acq.get_block()->start();
+            EXPECT(acq.get_block()->num_doppler_bins() == 8, "D = ceil(2*1000/250)");
+            run_acquisition(acq.get_block(), capture.data(), capture.size(), 1000, &ev);
+            EXPECT(ev == 1, "doppler centre: PRN 1 found through the moved grid");
+            const long dop = std::lround(gs.Acq_doppler_hz);
+            EXPECT(static_cast<double>(dop) == gs.Acq_doppler_hz && dop >= 500 && dop <= 2250 && (dop - 500) % 250 == 0,
+                "doppler centre: Acq_doppler_hz is a row of the grid centred on 1500 Hz");
+            EXPECT(std::abs(gs.Acq_doppler_hz - 1680.0) <= 666.0 && std::abs(gs.Acq_delay_samples - 524.0) < 1.0,
+                "doppler centre: 524 samples / 1680 Hz");
+            std::printf("doppler centre (%s init): delay %.0f doppler %.0f stat %.2f\n", before_init ? "before" : "after",
+                gs.Acq_delay_samples, gs.Acq_doppler_hz, acq.get_block()->test_statistics());
         }
 }
 
@@ -1980,6 +2018,7 @@ int main(int argc, char** argv)
     test_acquisition_repeat_steps(capture);
     test_acquisition_service(capture);
     test_acquisition_dwells(capture);
+    test_acquisition_doppler_center(capture);
     test_acquisition_bit_transition(capture);
     test_acquisition_cbyte(capture);
     test_multicorrelator(capture);

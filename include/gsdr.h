@@ -281,7 +281,15 @@ int gsdr_acq_set_local_code(gsdr_acq* acq, uint32_t slot, const float* code, uin
 int gsdr_acq_set_active_prns(gsdr_acq* acq, uint32_t nprn);
 
 /* Doppler setters (AcquisitionInterface, acquisition_interface.h:56-59).  They
- * rebuild the Doppler wipe-off grid on the device. */
+ * rebuild the Doppler wipe-off grid on the device, re-derive the forward-spectrum
+ * reuse (gsdr_acq_get_spectrum_reuse) and, with pfa > 0, recompute the threshold;
+ * the code spectra and the second step's settings stay.  The handle's buffers are
+ * sized by its number of Doppler bins: a call that would change
+ * ceil(2 doppler_max / doppler_step) is GSDR_E_UNSUPPORTED and doppler_step = 0 is
+ * GSDR_E_ARG, both leaving the handle as it was.  A handle created with an explicit
+ * num_doppler_bins keeps that count whatever the new maximum and step: its rows
+ * become -doppler_max + doppler_center + doppler_step * d, d < num_doppler_bins,
+ * exactly as if it had been created with the new values. */
 int gsdr_acq_set_doppler(gsdr_acq* acq, int32_t doppler_max, uint32_t doppler_step, int32_t doppler_center);
 
 /* Carrier wipe-off model of the Doppler grid (update_local_carrier,
@@ -328,7 +336,14 @@ int gsdr_acq_run(gsdr_acq* acq, const void* iq_host, uint32_t nblocks, uint64_t 
  * accumulated grid with the counter as the CFAR divisor (:534), against the
  * max_dwells threshold (:908).  iq_host: one block (consumed_samples items);
  * out: nprn results (num_dwells = dwell + 1).  Synchronous.  The caller keeps
- * the dwell FSM (positive / next dwell / negative after max_dwells). */
+ * the dwell FSM (positive / next dwell / negative after max_dwells).
+ * Dwell 0 restarts the grid wherever the previous attempt stopped, so an
+ * abandoned attempt needs no reset.  No other call on the handle touches the
+ * kept grid (gsdr_acq_run and the spectrum / grid dumps between two dwells
+ * leave the later dwells unchanged).  The grid is kept per PRN slot: change the
+ * active PRN count (gsdr_acq_set_active_prns) between attempts, not inside one.
+ * Valid on every handle, max_dwells = 1 and bit_transition_flag (which forces
+ * max_dwells to 1) included: dwell >= max_dwells is GSDR_E_ARG. */
 int gsdr_acq_run_dwell(gsdr_acq* acq, const void* iq_host, uint32_t dwell, uint64_t stamp, gsdr_acq_result* out);
 
 /* Device-resident form: iq_dev holds nblocks*max_dwells blocks, block j starting

@@ -188,14 +188,16 @@ class AcqResult:
 
 
 def acquire(x, code, fs, doppler_max, doppler_step, D=None, pfa=0.0, samples_per_chip=None,
-            samples_per_code=None, doppler_center=0, dwells=1, dtype=np.complex128, wipe=None, M_out=None):
+            samples_per_code=None, doppler_center=0, dwells=1, dtype=np.complex128, wipe=None, M_out=None,
+            doppler_bias=0):
     """One acquisition_core pass (single dwell, no bit transition) for one PRN.
-    x, code: complex64[N].  Returns AcqResult."""
+    x, code: complex64[N].  doppler_bias (d_doppler_bias, the GLONASS channel offset)
+    moves the carriers (:302-303) and not the reported doppler_hz (:535).  Returns AcqResult."""
     N = len(x)
     if D is None:
         D = num_doppler_bins(doppler_max, doppler_step)
     if wipe is None:
-        wipe = doppler_wipeoffs(fs, N, doppler_max, doppler_step, D, doppler_center)
+        wipe = doppler_wipeoffs(fs, N, doppler_max, doppler_step, D, doppler_center, doppler_bias)
     cf = fft_code(code, N, N, dtype=dtype)
     M = magnitude_grid(x, wipe, cf, dtype=dtype)
     if M_out is not None:
