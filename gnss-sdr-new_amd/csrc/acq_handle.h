@@ -141,7 +141,7 @@ inline int default_pk_variant(uint32_t N)
 {
     switch (N)
         {
-        case 4000: return 101;  // 99 with the correlate on the prime-factor 32 x 125 plan: +8 % over 99
+        case 4000: return 103;  // 101 (prime-factor 32 x 125 plan) on the 16-instruction 5-point transform, |z|^2 of two outputs packed: +3 % over 101
         case 16000: return 94;  // r04a: wave-local rows, +3 % over 93
         case 8000: return 61;
         case 2000: return 62;

@@ -873,6 +873,16 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                         rmax = __builtin_fmaxf(rmax, m);
                         if constexpr (STAT == 1) sum += m;
                     };
+                    // two outputs at once from a plan with PAIRS, their real parts in re and their
+                    // imaginary parts in im: both |z|^2 in one packed product and one packed
+                    // fused multiply-add -- the roundings of store's fmaf(x, x, y * y) --, the
+                    // maximum of three in one instruction
+                    auto store_pair = [&](c2 re, c2 im) {
+                        static_assert(!MP::PAIRS || STAT == 2, "pairs: row maximum only");
+                        const c2 m = __builtin_elementwise_fma(re, re, im * im);
+                        rmax = __builtin_fmaxf(__builtin_fmaxf(rmax, m.x), m.y);
+                    };
+                    static_assert(!MP::PAIRS || LANE, "plans with pairs: lane-order code rows");
                     if constexpr (STAGED)
                         {
                             // every wave has read its code values before any overwrites the buffer
@@ -881,7 +891,10 @@ __global__ void __launch_bounds__(MP::NT) __attribute__((amdgpu_waves_per_eu(WPE
                             auto mid = [&]() {
                                 if (q + 1 < np) stage_code(q + 1);
                             };
-                            if constexpr (LANE)
+                            if constexpr (MP::PAIRS)
+                                MP::template run<false, true>(lds, tw, load, gsdr::pk::PairStore<decltype(store), decltype(store_pair)>{store, store_pair},
+                                    hook, gsdr::pk::NoHook{}, mid, tws);
+                            else if constexpr (LANE)
                                 MP::template run<false, true>(lds, tw, load, store, hook, gsdr::pk::NoHook{}, mid, tws);
                             else
                                 MP::template run<false>(lds, tw, load, store, hook, pre, mid);

@@ -58,6 +58,17 @@ using RegPlan94 = RegFourStep<16, 512, 0, 1 | (16 << 4), NoPads<1000>, 10, 10, 1
 // differ from 70's by f32 rounding order (tests/test_gpu_acq_pk_prime_factor.py).  +8 % over 99
 // on the C2 bench; 99 stays as its A/B partner.  Measured on the way and not kept
 // (profiles/pfa101): the powers W_125^(c k) read from a table instead of chained (-2 %).
+// 103 is 101 with fewer instructions in the butterflies (PkPfaPlan4000Lean): the 5-point
+// transforms of the first stage's radix 25 and of the last stage as DftLean<5>, 16 packed
+// instructions instead of 18, and the last stage's outputs 1, 4 and 2, 3 handed to the row
+// statistic two at a time, |z|^2 of both in one packed product and one packed fused multiply-add
+// (144 of 2029 VALU instructions fewer per transform, LDS traffic and barriers unchanged; 120
+// VGPRs, no scratch, occupancy 4).  Other roundings in the row maxima, within the same bound
+// against the oracle as 101 (tests/test_gpu_acq_pk_lean_butterflies.py); the records stay the
+// argmax pass's.  +2.8 % / +3.3 % over 101 on the C2 bench; 101 stays as its A/B partner.
+// Measured on the way and not kept (profiles/lean103): the paired |z|^2 alone on Dft<5>'s own
+// values (the old id 102 again; bit-identical row maxima, 56 instructions fewer): +0.3 % /
+// +0.4 %, within three times the parent's spread.
 template <int ID, class MP, int PG_, int WPE_, int ST, class REG = void, int CS_ = kCodeVgpr, int TW_ = kTwGlobal, class CP = MP>
 struct PkVariant
 {
@@ -76,7 +87,8 @@ using PkVariants = PlanList<PkVariant<61, PkPlan<512, true, 20, 20, 20>, 1, 1, 1
     PkVariant<97, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLds>,
     PkVariant<98, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane>,
     PkVariant<99, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwLds>,
-    PkVariant<101, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwPfa, gsdr::pk::PkPfaPlan4000<256>>>;
+    PkVariant<101, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwPfa, gsdr::pk::PkPfaPlan4000<256>>,
+    PkVariant<103, PkPlan<256, 1, 25, 16, 10>, 16, 4, 2, void, kCodeLane, kTwPfa, gsdr::pk::PkPfaPlan4000Lean<256>>>;
 
 // f(PkVariant) -> int for variant id; `unknown` for an id not in the list (an
 // internal error in a launch: setup accepted the handle's id).
