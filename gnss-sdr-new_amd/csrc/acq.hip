@@ -20,6 +20,7 @@
 // (templates) and acq_common.hip, the launch sequences in acq_launch.h.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -289,6 +290,14 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
     rc = rebuild_wipeoffs(a);
     if (rc != GSDR_OK) return rc;
     compute_threshold(a);
+    // GSDR_ACQ_FINE=1: the fine-Doppler plan and buffers now instead of on the first
+    // call; a size it does not cover stays a valid handle (that call reports it)
+    const char* fine_env = std::getenv("GSDR_ACQ_FINE");
+    if (fine_env && fine_env[0] == '1' && fine_env[1] == '\0')
+        {
+            rc = fine_prepare(a);
+            if (rc != GSDR_OK && rc != GSDR_E_UNSUPPORTED) return rc;
+        }
     *out = guard.release();
     return GSDR_OK;
 }
@@ -313,6 +322,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
         a->d_iq, a->d_grid, a->d_rowbuf, a->d_keys, a->d_psum, a->d_fscratch, a->d_dgrid, a->d_tw_sub, a->d_scratch, a->d_slots, a->d_resk, a->d_acc, a->d_acc_slots};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
+    fine_free(a);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }

@@ -94,6 +94,31 @@ struct gsdr_acq
         float2* d_wipe{nullptr}; // max_prns x nbins rows of N
         float* d_freq{nullptr};
     } st2;
+    // fine-Doppler estimate (gsdr_acq_fine_doppler, acq_fine.hip): the L = 10 N point
+    // plan, its tables and scratch pool, built on the first call (or at create with
+    // GSDR_ACQ_FINE=1), and the per-call buffers, grown on demand
+    struct Fine
+    {
+        bool ready{false};
+        uint32_t L{0};
+        int r1{0};  // 0: one LDS plan; else the four-step's register radix (L = r1 * n2)
+        int nt{0};
+        gsdr::fft::Plan plan{};
+        gsdr::fft::Plan4 plan4{};
+        size_t lds_bytes{0};
+        float2* d_tw{nullptr};       // W_L
+        float2* d_tw_sub{nullptr};   // four-step: W_N2
+        float2* d_scratch{nullptr};  // four-step: kFineSlots rows of L complex
+        uint32_t* d_slots{nullptr};
+        void* d_iq{nullptr};         // the 10 ms window of the host forms
+        float2* d_codes{nullptr};
+        uint32_t codes_cap{0};
+        gsdr_acq_fine_request* d_req{nullptr};
+        gsdr_acq_fine_result* d_out{nullptr};
+        unsigned long long* d_keys{nullptr};
+        uint32_t req_cap{0};
+        float* d_spec{nullptr};      // gsdr_acq_dump_fine_spectrum: 80 N floats
+    } fine;
     std::mutex mu;
 };
 
@@ -165,6 +190,43 @@ inline int set_max_lds(const void* kernel, size_t bytes)
     return GSDR_OK;
 }
 
+// Event bracket around one stage launch when profiling is on (gsdr_acq_set_profiling): a
+// record owns its two events, taken from the handle's pool.
+struct StageTimer
+{
+    gsdr_acq* a;
+    hipStream_t s;
+    hipEvent_t ev0{nullptr};
+    StageTimer(gsdr_acq* a_, hipStream_t s_) : a(a_), s(s_) {}
+    hipEvent_t take()
+    {
+        hipEvent_t e = nullptr;
+        if (!a->prof_pool.empty())
+            {
+                e = a->prof_pool.back();
+                a->prof_pool.pop_back();
+            }
+        else if (hipEventCreate(&e) != hipSuccess)
+            e = nullptr;
+        return e;
+    }
+    void begin()
+    {
+        if (!a->profiling) return;
+        ev0 = take();
+        if (ev0) (void)hipEventRecord(ev0, s);
+    }
+    void end(int stage)
+    {
+        if (!a->profiling || !ev0) return;
+        hipEvent_t ev1 = take();
+        if (!ev1) return;
+        (void)hipEventRecord(ev1, s);
+        a->prof_recs.push_back({ev0, ev1, stage});
+        ev0 = nullptr;
+    }
+};
+
 // acq_common.hip
 AcqEnv read_acq_env();
 AcqView view_of(const gsdr_acq* a);
@@ -197,5 +259,9 @@ int launch_split_argmax(gsdr_acq* a, const AcqView& v, uint32_t nblocks, gsdr_ac
 int dispatch_static(gsdr_acq* a, const AcqView& v, const AcqOp& op);
 int dispatch_runtime(gsdr_acq* a, const AcqView& v, const AcqOp& op);
 int dispatch_four(gsdr_acq* a, const AcqView& v, const AcqOp& op);
+// acq_fine.hip: build the fine-Doppler plan and its buffers (no-op when built;
+// GSDR_E_UNSUPPORTED leaves the handle as it was), free them
+int fine_prepare(gsdr_acq* a);
+void fine_free(gsdr_acq* a);
 
 }  // namespace gsdr_acq_impl

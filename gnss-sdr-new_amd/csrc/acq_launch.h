@@ -32,42 +32,6 @@ int set_lds_attrs(size_t bytes)
     return rc == GSDR_OK ? GSDR_OK : GSDR_E_DEVICE;
 }
 
-// Event bracket around one stage launch when profiling is on.
-struct StageTimer
-{
-    gsdr_acq* a;
-    hipStream_t s;
-    hipEvent_t ev0{nullptr};
-    StageTimer(gsdr_acq* a_, hipStream_t s_) : a(a_), s(s_) {}
-    hipEvent_t take()
-    {
-        hipEvent_t e = nullptr;
-        if (!a->prof_pool.empty())
-            {
-                e = a->prof_pool.back();
-                a->prof_pool.pop_back();
-            }
-        else if (hipEventCreate(&e) != hipSuccess)
-            e = nullptr;
-        return e;
-    }
-    void begin()
-    {
-        if (!a->profiling) return;
-        ev0 = take();
-        if (ev0) (void)hipEventRecord(ev0, s);
-    }
-    void end(int stage)
-    {
-        if (!a->profiling || !ev0) return;
-        hipEvent_t ev1 = take();
-        if (!ev1) return;
-        (void)hipEventRecord(ev1, s);
-        a->prof_recs.push_back({ev0, ev1, stage});
-        ev0 = nullptr;
-    }
-};
-
 // The plan object a plan type's kernels take (LDS plan or four-step plan).
 template <class PT>
 const typename PT::PlanT& plan_of(const gsdr_acq* a)

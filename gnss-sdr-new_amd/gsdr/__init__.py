@@ -52,6 +52,8 @@ EXPORTED = [
     "gsdr_stream_read", "gsdr_firdes_low_pass", "gsdr_acq_resampler_plan", "gsdr_decim_create", "gsdr_decim_destroy",
     "gsdr_decim_output", "gsdr_decim_advance", "gsdr_acq_get_plan", "gsdr_acq_get_split",
     "gsdr_acq_dump_row_maxima",
+    "gsdr_acq_fine_doppler", "gsdr_acq_fine_doppler_stream", "gsdr_acq_dump_fine_spectrum", "gsdr_acq_get_fine_plan",
+    "gsdr_acq_get_fine_ready",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -193,6 +195,37 @@ ACQ_RESULT_DTYPE = np.dtype([
 assert ACQ_RESULT_DTYPE.itemsize == ctypes.sizeof(AcqResult)
 
 
+class AcqFineRequest(ctypes.Structure):
+    """gsdr_acq_fine_request: one fine-Doppler estimate of a call's 10 ms window."""
+    _fields_ = [
+        ("code_phase", ctypes.c_uint32),
+        ("coarse_doppler_hz", ctypes.c_float),
+        ("code_slot", ctypes.c_uint32),
+    ]
+
+
+class AcqFineResult(ctypes.Structure):
+    """gsdr_acq_fine_result."""
+    _fields_ = [
+        ("index", ctypes.c_uint32),
+        ("peak", ctypes.c_float),
+        ("freq_hz", ctypes.c_float),
+        ("doppler_hz", ctypes.c_double),
+        ("accepted", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
+ACQ_FINE_REQUEST_DTYPE = np.dtype([("code_phase", np.uint32), ("coarse_doppler_hz", np.float32),
+                                   ("code_slot", np.uint32)])
+ACQ_FINE_RESULT_DTYPE = np.dtype({
+    "names": [f for f, _ in AcqFineResult._fields_],
+    "formats": [np.uint32, np.float32, np.float32, np.float64, np.int32, np.int32],
+    "offsets": [getattr(AcqFineResult, f).offset for f, _ in AcqFineResult._fields_],
+    "itemsize": ctypes.sizeof(AcqFineResult)})
+assert ACQ_FINE_REQUEST_DTYPE.itemsize == ctypes.sizeof(AcqFineRequest)
+
+
 class CorrJob(ctypes.Structure):
     _fields_ = [
         ("channel", ctypes.c_int32),
@@ -250,6 +283,11 @@ def load():
     L.gsdr_acq_set_wipeoff.argtypes = [P, ctypes.c_int]
     L.gsdr_acq_get_spectrum_reuse.argtypes = [P, P, P]
     L.gsdr_acq_dump_spectra.argtypes = [P, P, P]
+    L.gsdr_acq_fine_doppler.argtypes = [P, P, P, U32, P, U32, P]
+    L.gsdr_acq_fine_doppler_stream.argtypes = [P, P, U64, P, U32, P, U32, P]
+    L.gsdr_acq_dump_fine_spectrum.argtypes = [P, P, P, U32, P]
+    L.gsdr_acq_get_fine_plan.argtypes = [P, P, P, P]
+    L.gsdr_acq_get_fine_ready.argtypes = [P, P]
     L.gsdr_corr_create.argtypes = [I, I, I, I, P]
     L.gsdr_corr_destroy.argtypes = [P]
     L.gsdr_corr_destroy.restype = None
@@ -587,6 +625,67 @@ class Acquisition:
         X = np.zeros((self.num_doppler_bins, self.fft_size), np.complex64)
         _check(load().gsdr_acq_dump_spectra(self._h, _ptr(iq), _ptr(X)))
         return X
+
+    # ---- fine Doppler (pcps_acquisition_fine_doppler_cc's estimate_Doppler)
+    def _fine_args(self, codes, requests):
+        codes = np.ascontiguousarray(codes, np.complex64)
+        if codes.ndim == 1:
+            codes = codes[None, :]
+        assert codes.ndim == 2 and codes.shape[1] == self.fft_size, codes.shape
+        if isinstance(requests, np.ndarray) and requests.dtype == ACQ_FINE_REQUEST_DTYPE:
+            req = np.ascontiguousarray(requests)
+        else:
+            req = np.zeros(len(requests), ACQ_FINE_REQUEST_DTYPE)
+            for i, r in enumerate(requests):
+                req[i] = tuple(r)
+        return codes, req
+
+    def fine_doppler(self, iq, codes, requests):
+        """gsdr_acq_fine_doppler: iq = 10 * fft_size host items, codes = rows of fft_size
+        complex64, requests = (code_phase, coarse_doppler_hz, code_slot) tuples or an
+        ACQ_FINE_REQUEST_DTYPE array -> structured array [len(requests)]."""
+        iq = self._items(iq)
+        codes, req = self._fine_args(codes, requests)
+        need = 10 * self.fft_size * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        out = np.zeros(len(req), ACQ_FINE_RESULT_DTYPE)
+        _check(load().gsdr_acq_fine_doppler(self._h, _ptr(iq), _ptr(codes), codes.shape[0], _ptr(req), len(req),
+                                            _ptr(out)))
+        return out
+
+    def fine_doppler_stream(self, ring, first_sample, codes, requests):
+        """gsdr_acq_fine_doppler_stream: the same on the Stream's items
+        [first_sample, first_sample + 10 * fft_size), read in place."""
+        codes, req = self._fine_args(codes, requests)
+        out = np.zeros(len(req), ACQ_FINE_RESULT_DTYPE)
+        _check(load().gsdr_acq_fine_doppler_stream(self._h, ring._h, int(first_sample), _ptr(codes), codes.shape[0],
+                                                   _ptr(req), len(req), _ptr(out)))
+        return out
+
+    def dump_fine_spectrum(self, iq, code, code_phase):
+        """gsdr_acq_dump_fine_spectrum: |X|^2 of all 80 * fft_size bins (float32)."""
+        iq = self._items(iq)
+        code = np.ascontiguousarray(code, np.complex64)
+        assert code.ndim == 1 and len(code) == self.fft_size
+        spec = np.zeros(80 * self.fft_size, np.float32)
+        _check(load().gsdr_acq_dump_fine_spectrum(self._h, _ptr(iq), _ptr(code), int(code_phase), _ptr(spec)))
+        return spec
+
+    @property
+    def fine_plan(self):
+        """(L, r1, n2) of the handle's fine transform (gsdr_acq_get_fine_plan): r1 = 0 for
+        one LDS plan, else the four-step L = r1 * n2."""
+        L, r1, n2 = ctypes.c_uint32(), ctypes.c_int32(), ctypes.c_uint32()
+        _check(load().gsdr_acq_get_fine_plan(self._h, ctypes.byref(L), ctypes.byref(r1), ctypes.byref(n2)))
+        return L.value, r1.value, n2.value
+
+    @property
+    def fine_ready(self):
+        """True once the handle holds its fine plan and buffers (gsdr_acq_get_fine_ready): after
+        the first fine-Doppler call, or from create on with GSDR_ACQ_FINE=1."""
+        r = ctypes.c_int32(-1)
+        _check(load().gsdr_acq_get_fine_ready(self._h, ctypes.byref(r)))
+        return bool(r.value)
 
 
 class Correlator:

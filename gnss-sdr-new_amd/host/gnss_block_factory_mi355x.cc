@@ -3,6 +3,7 @@
 #include "beidou_b1i_pcps_acquisition_mi355x.h"
 #include "galileo_e1_pcps_ambiguous_acquisition_mi355x.h"
 #include "gnss_tracking_mi355x.h"
+#include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_mi355x.h"
 #include "gsdr.h"
 
@@ -26,6 +27,9 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
     const int device = device_for_channel(configuration, role, channel);
     if (implementation == "GPS_L1_CA_PCPS_Acquisition_MI355X")
         return std::make_unique<GpsL1CaPcpsAcquisitionMI355X>(configuration, role, in_streams, out_streams, device);
+    if (implementation == "GPS_L1_CA_PCPS_Acquisition_Fine_Doppler_MI355X")
+        return std::make_unique<GpsL1CaPcpsAcquisitionFineDopplerMI355X>(configuration, role, in_streams, out_streams,
+            device);
     if (implementation == "Galileo_E1_PCPS_Ambiguous_Acquisition_MI355X")
         return std::make_unique<GalileoE1PcpsAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);

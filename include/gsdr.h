@@ -439,6 +439,70 @@ int gsdr_acq_read_profile_intervals(gsdr_acq* acq, const void* ref_event, int st
  * D rows x fft_size complex<float> (= FFT(x .* w_d)). */
 int gsdr_acq_dump_spectra(gsdr_acq* acq, const void* iq_host, float* spectra_host);
 
+/* ---- Fine Doppler: the second stage of pcps_acquisition_fine_doppler_cc
+ * (estimate_Doppler, pcps_acquisition_fine_doppler_cc.cc:346-419).  With N = fft_size,
+ * the block wipes the code off 10 ms of signal (L = 10 N samples) with the replica
+ * aligned to the coarse code phase, zero-pads to M = 8 L = 80 N points, takes one
+ * M-point FFT and the first maximum of |X|^2: a Doppler on a grid of fs / (80 N) Hz,
+ * accepted if within 1000 Hz of the coarse one.  The engine computes the padded
+ * transform as eight L-point transforms of the wiped signal times a phase ramp, one
+ * workgroup per (request, residue of the bin index mod 8), and never stores the
+ * spectrum.  The replica alignment is the reference's, quirk included (:365-371):
+ * std::rotate(c, c + (N - shift), c + N - 1) ends its range at N - 1, so only the
+ * first N - 1 samples rotate, sample N - 1 stays, and shift 0 and 1 both leave the row
+ * unchanged; the ten periods are copies of that row (:373-376).
+ * Only handles on 1 ms blocks (consumed_samples == fft_size, no bit_transition_flag)
+ * and sizes whose L has an FFT plan (2^a 3^b 5^c; up to 20352 points in LDS, else
+ * R x N2 with R in {8, 10, 12, 16, 20, 25}) are served: GSDR_E_UNSUPPORTED otherwise,
+ * the handle unchanged.  The plan, its tables and its scratch rows (a pool of 32 rows of L
+ * complex, 64 from the first call with more than four requests on) are built on the
+ * first call (at create with GSDR_ACQ_FINE=1 in the environment) and freed with the
+ * handle.  The calls leave the coarse stage's state alone (a call between two
+ * gsdr_acq_run_dwell dwells does not change the later dwell). */
+typedef struct gsdr_acq_fine_request
+{
+    uint32_t code_phase;      /* Acq_delay_samples of the coarse step, < fft_size (shift_index, :365) */
+    float coarse_doppler_hz;  /* Acq_doppler_hz of the coarse step (:407) */
+    uint32_t code_slot;       /* which of the call's code rows */
+} gsdr_acq_fine_request;
+
+typedef struct gsdr_acq_fine_result
+{
+    uint32_t index;     /* argmax of |X|^2 over the 80 N bins, first maximum (:385-388) */
+    float peak;         /* |X|^2 there */
+    float freq_hz;      /* fftFreqBins[index] (:394-404): float operands, formed in double, rounded once */
+    double doppler_hz;  /* freq_hz if accepted, else coarse_doppler_hz (:407-416) */
+    int32_t accepted;   /* std::abs(freq_hz - coarse_doppler_hz) < 1000 */
+    int32_t pad;
+} gsdr_acq_fine_result;
+
+/* estimate_Doppler (:346-419) for nreq requests on one 10 ms window in one launch.
+ * iq_host: 10 * fft_size items (item_type); codes: ncodes rows of fft_size
+ * complex<float>, each the replica set_local_code gets
+ * (gps_l1_ca_code_gen_complex_sampled, :363); out: nreq records.  Null pointers,
+ * nreq = 0, code_phase >= fft_size and code_slot >= ncodes are GSDR_E_ARG.
+ * Synchronous.  With gsdr_acq_set_profiling enabled the transform kernel is recorded
+ * as stage [0] and the finish kernel as stage [2]. */
+int gsdr_acq_fine_doppler(gsdr_acq* acq, const void* iq_host, const float* codes, uint32_t ncodes,
+    const gsdr_acq_fine_request* requests, uint32_t nreq, gsdr_acq_fine_result* out);
+/* The same on the ring's items [first_sample, first_sample + 10 * fft_size), read in
+ * place (the d_10_ms_buffer copy of :494, :518-538 is not made); ordered against the
+ * ring's pushes as gsdr_acq_run_stream is.  Synchronous (results on the host). */
+int gsdr_acq_fine_doppler_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_sample, const float* codes,
+    uint32_t ncodes, const gsdr_acq_fine_request* requests, uint32_t nreq, gsdr_acq_fine_result* out_host);
+/* Debug/verification, as gsdr_acq_dump_grid is for the coarse grid: p_tmp_vector of
+ * :384-385, the |X|^2 of all 80 * fft_size bins for one code row and code phase,
+ * written by the same kernels with a storing functor.  Synchronous. */
+int gsdr_acq_dump_fine_spectrum(gsdr_acq* acq, const void* iq_host, const float* code, uint32_t code_phase,
+    float* spectrum_host);
+/* The engine of the handle's fine transform (replaces the FFTW plan of :355): *L = 10 *
+ * fft_size; *r1 = 0 and *n2 = L for one LDS plan, else the four-step L = r1 * n2.  Host
+ * only; any output pointer may be null; GSDR_E_UNSUPPORTED as above. */
+int gsdr_acq_get_fine_plan(const gsdr_acq* acq, uint32_t* L, int32_t* r1, uint32_t* n2);
+/* *ready = 1 once the handle holds its fine plan, tables and scratch pool: after the first
+ * fine-Doppler call, or from create on with GSDR_ACQ_FINE=1 (and a size that has a plan). */
+int gsdr_acq_get_fine_ready(gsdr_acq* acq, int32_t* ready);
+
 /* ======================================================================== */
 /* Tracking multicorrelator (Cpu_Multicorrelator_Real_Codes / Cpu_Multicorrelator) */
 /* ======================================================================== */
