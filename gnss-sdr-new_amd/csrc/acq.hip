@@ -16,6 +16,10 @@
 //   K_second          per (b,p), peak-ratio mode only: recompute row d*, second peak outside
 //                     the +-1 chip window with the reference's wrap      (:546-612)
 //
+//   K_pair    paired codes (pcps_cccwsr_acquisition_cc, galileo_pcps_8ms_acquisition_cc): the
+//                     two replicas of a pair, the block's input power and the merge of a
+//                     pair's two slot records, around the kernels above (acq_pair.hip)
+//
 // This unit is the C ABI.  The kernels are in acq_kernels.h / acq_split_kernels.h
 // (templates) and acq_common.hip, the launch sequences in acq_launch.h.
 #include <algorithm>
@@ -32,15 +36,26 @@
 
 using namespace gsdr_acq_impl;
 
-namespace
-{
-
-int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op)
+int gsdr_acq_impl::dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op)
 {
     if (a->variant >= 20) return dispatch_four(a, v, op);
     if (a->variant >= 10) return dispatch_runtime(a, v, op);
     return dispatch_static(a, v, op);
 }
+
+int gsdr_acq_impl::code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
+{
+    AcqOp op{AcqOp::CodeFft};
+    op.first_slot = first_slot;
+    op.nslots = nslots;
+    const int rc = dispatch(a, view_of(a), op);
+    // the refreshed slots' lane-order copies, behind their spectra on the handle's stream
+    if (rc != GSDR_OK || !a->d_code_lane) return rc;
+    return launch_code_lane_order(a, first_slot, nslots);
+}
+
+namespace
+{
 
 // AcqOp::Run of nblocks blocks at iq (device), results to res (device).
 int run_blocks(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, uint64_t stamp0,
@@ -67,17 +82,6 @@ int read_results(gsdr_acq* a, gsdr_acq_result* out, size_t n)
     GSDR_HIP(hipMemcpyAsync(out, a->d_res, n * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost, a->stream));
     GSDR_HIP(hipStreamSynchronize(a->stream));
     return GSDR_OK;
-}
-
-int code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots)
-{
-    AcqOp op{AcqOp::CodeFft};
-    op.first_slot = first_slot;
-    op.nslots = nslots;
-    const int rc = dispatch(a, view_of(a), op);
-    // the refreshed slots' lane-order copies, behind their spectra on the handle's stream
-    if (rc != GSDR_OK || !a->d_code_lane) return rc;
-    return launch_code_lane_order(a, first_slot, nslots);
 }
 
 // update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), float arithmetic:
@@ -323,6 +327,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
     for (void* p : bufs)
         if (p) (void)hipFree(p);
     fine_free(a);
+    pairs_free(a);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -372,6 +377,7 @@ int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* pr
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
     a->nprn = nprn;
+    a->pairs.npairs = 0;
     return GSDR_OK;
 }
 
@@ -391,6 +397,7 @@ int gsdr_acq_set_local_code(gsdr_acq* a, uint32_t slot, const float* code, uint3
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
     if (a->nprn <= slot) a->nprn = slot + 1;
+    a->pairs.npairs = 0;
     return GSDR_OK;
 }
 
@@ -401,6 +408,7 @@ int gsdr_acq_set_active_prns(gsdr_acq* a, uint32_t nprn)
         a->conf.max_prns);
     std::lock_guard<std::mutex> lk(a->mu);
     a->nprn = nprn;
+    a->pairs.npairs = 0;
     return GSDR_OK;
 }
 

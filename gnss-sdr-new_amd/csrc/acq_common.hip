@@ -415,7 +415,8 @@ AcqParams params_of(const gsdr_acq* a, const AcqView& v)
     ap.samples_per_chip = a->conf.samples_per_chip;
     ap.dwells = a->K;
     ap.threshold = a->threshold;
-    ap.cfar = a->conf.pfa > 0.0f ? 1 : 0;
+    // a pair run reads no second peak: its launches are the CFAR sequence's (acq_pair.hip)
+    ap.cfar = (a->conf.pfa > 0.0f || a->pairs.running) ? 1 : 0;
     ap.eff = a->eff;
     ap.out_off = a->N - a->eff;
     ap.counter = a->K;

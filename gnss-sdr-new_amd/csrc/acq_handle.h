@@ -119,6 +119,17 @@ struct gsdr_acq
         uint32_t req_cap{0};
         float* d_spec{nullptr};      // gsdr_acq_dump_fine_spectrum: 80 N floats
     } fine;
+    // paired-code acquisition (gsdr_acq_set_code_pairs / gsdr_acq_run_pairs, acq_pair.hip):
+    // pair q holds code slots 2 q and 2 q + 1; the buffers are built by the first
+    // gsdr_acq_set_code_pairs
+    struct Pairs
+    {
+        uint32_t npairs{0};       // > 0: the code slots hold pairs
+        bool running{false};      // a pair run's launches: no second-peak pass (params_of)
+        float2* d_in{nullptr};    // the caller's two arguments: 2 x (max_prns / 2) rows of N
+        float* d_power{nullptr};  // max_blocks input powers
+        gsdr_acq_pair_result* d_out{nullptr};  // max_blocks x (max_prns / 2) records
+    } pairs;
     std::mutex mu;
 };
 
@@ -263,5 +274,11 @@ int dispatch_four(gsdr_acq* a, const AcqView& v, const AcqOp& op);
 // GSDR_E_UNSUPPORTED leaves the handle as it was), free them
 int fine_prepare(gsdr_acq* a);
 void fine_free(gsdr_acq* a);
+// acq_pair.hip: free the pair buffers
+void pairs_free(gsdr_acq* a);
+// acq.hip: the per-plan dispatch of an op, and the code spectra (with their lane-order
+// copies) of slots [first_slot, first_slot + nslots) from their staged codes
+int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op);
+int code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots);
 
 }  // namespace gsdr_acq_impl

@@ -54,6 +54,7 @@ EXPORTED = [
     "gsdr_acq_dump_row_maxima",
     "gsdr_acq_fine_doppler", "gsdr_acq_fine_doppler_stream", "gsdr_acq_dump_fine_spectrum", "gsdr_acq_get_fine_plan",
     "gsdr_acq_get_fine_ready",
+    "gsdr_acq_set_code_pairs", "gsdr_acq_run_pairs", "gsdr_acq_run_pairs_stream", "gsdr_acq_dump_pair_rows",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -226,6 +227,34 @@ ACQ_FINE_RESULT_DTYPE = np.dtype({
 assert ACQ_FINE_REQUEST_DTYPE.itemsize == ctypes.sizeof(AcqFineRequest)
 
 
+class AcqPairResult(ctypes.Structure):
+    """gsdr_acq_pair_result: one (block, pair) outcome of gsdr_acq_run_pairs."""
+    _fields_ = [
+        ("prn", ctypes.c_uint32),
+        ("doppler_index", ctypes.c_uint32),
+        ("code_phase", ctypes.c_uint32),
+        ("member", ctypes.c_uint32),
+        ("doppler_hz", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+        ("mag", ctypes.c_float),
+        ("input_power", ctypes.c_float),
+        ("test_statistic", ctypes.c_float),
+        ("pad2", ctypes.c_float),
+        ("acq_delay_samples", ctypes.c_double),
+        ("samplestamp", ctypes.c_uint64),
+    ]
+
+
+ACQ_PAIR_RESULT_DTYPE = np.dtype([
+    ("prn", np.uint32), ("doppler_index", np.uint32), ("code_phase", np.uint32), ("member", np.uint32),
+    ("doppler_hz", np.int32), ("pad", np.int32), ("mag", np.float32), ("input_power", np.float32),
+    ("test_statistic", np.float32), ("pad2", np.float32), ("acq_delay_samples", np.float64),
+    ("samplestamp", np.uint64)])
+assert ACQ_PAIR_RESULT_DTYPE.itemsize == ctypes.sizeof(AcqPairResult)
+assert all(ACQ_PAIR_RESULT_DTYPE.fields[f][1] == getattr(AcqPairResult, f).offset for f, _ in AcqPairResult._fields_)
+PAIR_AS_IS, PAIR_SUM_DIFF_J = 0, 1
+
+
 class CorrJob(ctypes.Structure):
     _fields_ = [
         ("channel", ctypes.c_int32),
@@ -288,6 +317,11 @@ def load():
     L.gsdr_acq_dump_fine_spectrum.argtypes = [P, P, P, U32, P]
     L.gsdr_acq_get_fine_plan.argtypes = [P, P, P, P]
     L.gsdr_acq_get_fine_ready.argtypes = [P, P]
+    if hasattr(L, "gsdr_acq_set_code_pairs"):  # (an earlier build selected by GSDR_LIB for an A/B lacks them)
+        L.gsdr_acq_set_code_pairs.argtypes = [P, I, P, P, P, U32]
+        L.gsdr_acq_run_pairs.argtypes = [P, P, U32, U64, P]
+        L.gsdr_acq_run_pairs_stream.argtypes = [P, P, U64, U32, U64, P]
+        L.gsdr_acq_dump_pair_rows.argtypes = [P, P, P]
     L.gsdr_corr_create.argtypes = [I, I, I, I, P]
     L.gsdr_corr_destroy.argtypes = [P]
     L.gsdr_corr_destroy.restype = None
@@ -686,6 +720,78 @@ class Acquisition:
         r = ctypes.c_int32(-1)
         _check(load().gsdr_acq_get_fine_ready(self._h, ctypes.byref(r)))
         return bool(r.value)
+
+    # ---- paired codes (pcps_cccwsr_acquisition_cc, galileo_pcps_8ms_acquisition_cc)
+    def set_code_pairs(self, kind, first, second, prns):
+        """gsdr_acq_set_code_pairs: first / second = [npairs, fft_size] complex64; pair q takes
+        code slots 2 q and 2 q + 1.  PAIR_AS_IS: the members are the rows (the 8 ms block's
+        code A and code B); PAIR_SUM_DIFF_J: first - j second and first + j second (CCCWSR's
+        set_local_code(code_data, code_pilot))."""
+        first = np.ascontiguousarray(first, np.complex64)
+        second = np.ascontiguousarray(second, np.complex64)
+        prns = np.ascontiguousarray(prns, np.uint32)
+        assert first.ndim == 2 and first.shape == second.shape == (len(prns), self.fft_size), (first.shape, second.shape)
+        _check(load().gsdr_acq_set_code_pairs(self._h, int(kind), _ptr(first), _ptr(second), _ptr(prns), len(prns)))
+        self.nprn = 2 * len(prns)
+        self.npairs = len(prns)
+
+    def run_pairs(self, iq, nblocks=1, stamp0=0):
+        """gsdr_acq_run_pairs: nblocks * fft_size host items, each block a grid of its own ->
+        structured array [nblocks, npairs] (ACQ_PAIR_RESULT_DTYPE); pair_decide applies the
+        dwell rule."""
+        iq = self._items(iq)
+        need = nblocks * self.fft_size * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        npairs = getattr(self, "npairs", 0)
+        out = np.zeros(nblocks * max(npairs, 1), ACQ_PAIR_RESULT_DTYPE)
+        _check(load().gsdr_acq_run_pairs(self._h, _ptr(iq), int(nblocks), int(stamp0), _ptr(out)))
+        return out.reshape(nblocks, npairs)
+
+    def run_pairs_stream(self, ring, first_sample, nblocks=1, stamp0=0):
+        """gsdr_acq_run_pairs_stream: the same on a Stream's items from first_sample."""
+        npairs = getattr(self, "npairs", 0)
+        out = np.zeros(nblocks * max(npairs, 1), ACQ_PAIR_RESULT_DTYPE)
+        _check(load().gsdr_acq_run_pairs_stream(self._h, ring._h, int(first_sample), int(nblocks), int(stamp0),
+                                                _ptr(out)))
+        return out.reshape(nblocks, npairs)
+
+    def dump_pair_rows(self, iq):
+        """gsdr_acq_dump_pair_rows: the two members' normalised row maxima of one block,
+        float32 [num_doppler_bins, npairs, 2]."""
+        iq = self._items(iq)
+        npairs = getattr(self, "npairs", 0)
+        m = np.zeros((self.num_doppler_bins, max(npairs, 1), 2), np.float32)
+        _check(load().gsdr_acq_dump_pair_rows(self._h, _ptr(iq), _ptr(m)))
+        return m
+
+
+def pair_decide(records, threshold, carry_mag):
+    """The dwell rule of the two paired-code blocks on one satellite's records, one per
+    dwell in order (a column of run_pairs) -> (record, positive, num_dwells).
+
+    carry_mag=True is pcps_cccwsr_acquisition_cc: d_mag and the synchro fields survive from
+    dwell to dwell (:157, :191, :334-341), so the statistic after dwell k is
+    max(mag_0..mag_k) / input_power_k, the earliest dwell keeps a tie, and delay, Doppler
+    and stamp are those of the dwell that holds the maximum.  carry_mag=False is
+    galileo_pcps_8ms_acquisition_cc, which zeroes both at every dwell (:238-239).  Both
+    stop at the first dwell whose statistic exceeds the threshold, else after the last."""
+    records = np.asarray(records)
+    assert records.dtype == ACQ_PAIR_RESULT_DTYPE and records.ndim == 1 and len(records) > 0
+    thr = np.float32(threshold)
+    held = None
+    for k in range(len(records)):
+        rec = records[k].copy()
+        if carry_mag:
+            if held is None or held["mag"] < rec["mag"]:
+                held = rec.copy()
+            out = held.copy()
+            out["input_power"] = rec["input_power"]
+            out["test_statistic"] = np.float32(out["mag"]) / np.float32(rec["input_power"])
+        else:
+            out = rec
+        if np.float32(out["test_statistic"]) > thr:
+            return out, True, k + 1
+    return out, False, len(records)
 
 
 class Correlator:

@@ -2,6 +2,7 @@
 
 #include "beidou_b1i_pcps_acquisition_mi355x.h"
 #include "galileo_e1_pcps_ambiguous_acquisition_mi355x.h"
+#include "galileo_e1_pcps_pair_acquisition_mi355x.h"
 #include "gnss_tracking_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_mi355x.h"
@@ -32,6 +33,12 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
             device);
     if (implementation == "Galileo_E1_PCPS_Ambiguous_Acquisition_MI355X")
         return std::make_unique<GalileoE1PcpsAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,
+            device);
+    if (implementation == "Galileo_E1_PCPS_CCCWSR_Ambiguous_Acquisition_MI355X")
+        return std::make_unique<GalileoE1PcpsCccwsrAmbiguousAcquisitionMI355X>(configuration, role, in_streams,
+            out_streams, device);
+    if (implementation == "Galileo_E1_PCPS_8ms_Ambiguous_Acquisition_MI355X")
+        return std::make_unique<GalileoE1Pcps8msAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);
     if (implementation == "BEIDOU_B1I_PCPS_Acquisition_MI355X")
         return std::make_unique<BeidouB1iPcpsAcquisitionMI355X>(configuration, role, in_streams, out_streams, device);

@@ -503,6 +503,63 @@ int gsdr_acq_get_fine_plan(const gsdr_acq* acq, uint32_t* L, int32_t* r1, uint32
  * fine-Doppler call, or from create on with GSDR_ACQ_FINE=1 (and a size that has a plan). */
 int gsdr_acq_get_fine_ready(gsdr_acq* acq, int32_t* ready);
 
+/* ---- Paired-code acquisition: pcps_cccwsr_acquisition_cc (Galileo E1 CCCWSR) and
+ * galileo_pcps_8ms_acquisition_cc (8 ms PCPS).  Both correlate every Doppler row with
+ * two replicas per satellite; the row's value is the larger of the two row maxima ('>=':
+ * the first member keeps a tie, pcps_cccwsr_acquisition_cc.cc:322), the answer the
+ * first row, scanning upwards with strict '<' (:334), that holds the grid maximum, and
+ * mag / input_power the statistic (:360).  Pair q occupies the handle's ordinary code
+ * slots 2 q (member 0) and 2 q + 1 (member 1), so the forward and correlate kernels are
+ * the plain search's.  Only handles on blocks of fft_size items (consumed_samples ==
+ * fft_size), with max_dwells 1 and no bit_transition_flag are served:
+ * GSDR_E_UNSUPPORTED otherwise, the handle unchanged.  Neither reference block
+ * accumulates its grid over dwells: each block of a call is a grid of its own, and the
+ * dwell rule over the blocks' records is the caller's. */
+#define GSDR_ACQ_PAIR_AS_IS 0      /* members first[q], second[q]: the 8 ms block's code A and code B */
+#define GSDR_ACQ_PAIR_SUM_DIFF_J 1 /* members first - j second, first + j second: CCCWSR's
+                                    * d_correlation_plus = data + j pilot and d_correlation_minus
+                                    * (:301-308) are the correlations with these two replicas */
+
+typedef struct gsdr_acq_pair_result
+{
+    uint32_t prn;
+    uint32_t doppler_index;   /* first row holding the grid maximum */
+    uint32_t code_phase;      /* indext, < fft_size */
+    uint32_t member;          /* 0 or 1: which replica holds it */
+    int32_t doppler_hz;       /* Acq_doppler_hz */
+    int32_t pad;
+    float mag;                /* d_mag: the maximum / (float(N) float(N))^2, in float (:247, :316) */
+    float input_power;        /* d_input_power: sum |x|^2 / fft_size of the block (:250-252) */
+    float test_statistic;     /* mag / input_power (:360) */
+    float pad2;
+    double acq_delay_samples; /* code_phase % (uint32_t)samples_per_code (:337) */
+    uint64_t samplestamp;     /* the block's first sample: stamp0 + b * consumed_samples */
+} gsdr_acq_pair_result;
+
+/* The replicas of npairs satellites: first and second are npairs rows of fft_size
+ * complex<float>, prn their ids (CCCWSR: set_local_code(code_data, code_pilot), :126-144,
+ * with GSDR_ACQ_PAIR_SUM_DIFF_J).  The members are formed on the device and transformed as
+ * gsdr_acq_set_local_codes transforms its rows; the active slot count becomes 2 npairs and
+ * the handle holds pairs until gsdr_acq_set_local_codes, gsdr_acq_set_local_code or
+ * gsdr_acq_set_active_prns is called.  Null pointers, an unknown kind, npairs = 0 and
+ * 2 npairs > max_prns are GSDR_E_ARG. */
+int gsdr_acq_set_code_pairs(gsdr_acq* acq, int kind, const float* first, const float* second, const uint32_t* prn,
+    uint32_t npairs);
+/* nblocks independent grids over the pairs: iq_host holds nblocks * fft_size items, out
+ * [nblocks][npairs] records.  The winner is the first cell in the order (row ascending,
+ * member 0 before member 1, index ascending) that holds the maximum.  Synchronous.
+ * GSDR_E_STATE on a handle that holds no pairs.  With gsdr_acq_set_profiling enabled the
+ * input-power and merge kernels are recorded in stage [2]. */
+int gsdr_acq_run_pairs(gsdr_acq* acq, const void* iq_host, uint32_t nblocks, uint64_t stamp0,
+    gsdr_acq_pair_result* out);
+/* The same on the ring's items from first_sample, read in place; ordered against the
+ * ring's pushes as gsdr_acq_run_stream is.  Synchronous (results on the host). */
+int gsdr_acq_run_pairs_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_sample, uint32_t nblocks,
+    uint64_t stamp0, gsdr_acq_pair_result* out_host);
+/* Debug/verification: magt_plus and magt_minus (:316-320) of every Doppler row of one
+ * block, out [num_doppler_bins][npairs][2] normalised row maxima, on every FFT plan. */
+int gsdr_acq_dump_pair_rows(gsdr_acq* acq, const void* iq_host, float* out);
+
 /* ======================================================================== */
 /* Tracking multicorrelator (Cpu_Multicorrelator_Real_Codes / Cpu_Multicorrelator) */
 /* ======================================================================== */
