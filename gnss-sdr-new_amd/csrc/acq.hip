@@ -16,6 +16,9 @@
 //   K_second          per (b,p), peak-ratio mode only: recompute row d*, second peak outside
 //                     the +-1 chip window with the reference's wrap      (:546-612)
 //
+//   K_quick   QuickSync (pcps_quicksync_acquisition_cc): the folded code, the folding forward
+//                     transform in place of K_forward, the item's input power and the check of
+//                     the p delays the folded winner stands for (acq_quicksync.hip)
 //   K_pair    paired codes (pcps_cccwsr_acquisition_cc, galileo_pcps_8ms_acquisition_cc): the
 //                     two replicas of a pair, the block's input power and the merge of a
 //                     pair's two slot records, around the kernels above (acq_pair.hip)
@@ -328,6 +331,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
         if (p) (void)hipFree(p);
     fine_free(a);
     pairs_free(a);
+    quicksync_free(a);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -378,6 +382,7 @@ int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* pr
     GSDR_HIP(hipStreamSynchronize(a->stream));
     a->nprn = nprn;
     a->pairs.npairs = 0;
+    a->qs.ncodes = 0;
     return GSDR_OK;
 }
 
@@ -398,6 +403,7 @@ int gsdr_acq_set_local_code(gsdr_acq* a, uint32_t slot, const float* code, uint3
     GSDR_HIP(hipStreamSynchronize(a->stream));
     if (a->nprn <= slot) a->nprn = slot + 1;
     a->pairs.npairs = 0;
+    a->qs.ncodes = 0;
     return GSDR_OK;
 }
 
@@ -409,6 +415,7 @@ int gsdr_acq_set_active_prns(gsdr_acq* a, uint32_t nprn)
     std::lock_guard<std::mutex> lk(a->mu);
     a->nprn = nprn;
     a->pairs.npairs = 0;
+    a->qs.ncodes = 0;
     return GSDR_OK;
 }
 

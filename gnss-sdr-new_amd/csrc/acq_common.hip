@@ -375,6 +375,7 @@ namespace gsdr_acq_impl
 //       plan) or one PRN per 512-lane workgroup (1, the default)
 //   GSDR_ACQ_CORR_VARIANT  a packed correlate variant (PkVariants, acq_pk.hip) other
 //       than default_pk_variant's, for tests
+// (GSDR_ACQ_QS_CAND_LOOP is read by gsdr_acq_set_quicksync, acq_quicksync.hip.)
 AcqEnv read_acq_env()
 {
     AcqEnv e;
@@ -416,7 +417,8 @@ AcqParams params_of(const gsdr_acq* a, const AcqView& v)
     ap.dwells = a->K;
     ap.threshold = a->threshold;
     // a pair run reads no second peak: its launches are the CFAR sequence's (acq_pair.hip)
-    ap.cfar = (a->conf.pfa > 0.0f || a->pairs.running) ? 1 : 0;
+    // (nor does a QuickSync run, acq_quicksync.hip)
+    ap.cfar = (a->conf.pfa > 0.0f || a->pairs.running || a->qs.running) ? 1 : 0;
     ap.eff = a->eff;
     ap.out_off = a->N - a->eff;
     ap.counter = a->K;
@@ -473,11 +475,21 @@ int launch_wipeoff(gsdr_acq* a, float2* wipe, uint32_t rows, const float* freqs)
     return GSDR_OK;
 }
 
+int launch_wipeoff_long(gsdr_acq* a, float2* wipe, uint32_t rows, uint32_t len)
+{
+    const gsdr_acq_conf& c = a->conf;
+    hipLaunchKernelGGL(acq_wipeoff_kernel, dim3(rows), dim3(256), 0, a->stream, wipe, len, (float)c.fs_in, c.doppler_max,
+        c.doppler_center, (int32_t)c.doppler_step, c.doppler_bias, (const float*)nullptr, GSDR_WIPE_EXACT);
+    GSDR_HIP(hipGetLastError());
+    return GSDR_OK;
+}
+
 int rebuild_wipeoffs(gsdr_acq* a)
 {
     a->xm = grid_xmap(a);
     // rows 0..q-1 suffice with the reuse (the other rows would be their shifts)
-    const int rc = launch_wipeoff(a, a->d_wipe, a->xm.q, nullptr);
+    int rc = launch_wipeoff(a, a->d_wipe, a->xm.q, nullptr);
+    if (rc == GSDR_OK) rc = quicksync_rebuild_wipeoffs(a);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
     return GSDR_OK;

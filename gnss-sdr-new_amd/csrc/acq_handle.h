@@ -130,6 +130,22 @@ struct gsdr_acq
         float* d_power{nullptr};  // max_blocks input powers
         gsdr_acq_pair_result* d_out{nullptr};  // max_blocks x (max_prns / 2) records
     } pairs;
+    // QuickSync acquisition (gsdr_acq_set_quicksync / gsdr_acq_run_quicksync, acq_quicksync.hip):
+    // the handle's fft_size is Nf = spc / p; the buffers are built by gsdr_acq_set_quicksync
+    struct Quick
+    {
+        uint32_t p{0};            // folding factor (> 0: configured)
+        uint32_t spc{0};          // samples per code (p Nf); an item is L = p spc samples
+        uint32_t ncodes{0};       // > 0: the code slots hold folded QuickSync codes
+        bool running{false};      // a QuickSync run's launches: the folding forward, no second-peak pass
+        bool cand_loop{false};    // GSDR_ACQ_QS_CAND_LOOP=1: one workgroup per (item, slot) over the p candidates
+        void* d_iq{nullptr};      // host items' staging: max_blocks x L items of the handle's type
+        float2* d_wipe{nullptr};  // D rows (xm.q with the spectrum reuse) of L
+        float2* d_codes{nullptr}; // max_prns unfolded codes of spc
+        float* d_power{nullptr};  // max_blocks input powers
+        float* d_cand{nullptr};   // max_blocks x max_prns x p candidate powers
+        gsdr_acq_quicksync_result* d_out{nullptr};  // max_blocks x max_prns records
+    } qs;
     std::mutex mu;
 };
 
@@ -250,6 +266,8 @@ float step_two_threshold(const gsdr_acq* a);
 // (block, PRN) or (dwells) per (block, PRN, dwell), the dwell decision, the second peak
 // of gsdr_acq_run_dwell's accumulated grid
 int launch_wipeoff(gsdr_acq* a, float2* wipe, uint32_t rows, const float* freqs);
+// the main grid's first `rows` rows over len samples each (QuickSync's items)
+int launch_wipeoff_long(gsdr_acq* a, float2* wipe, uint32_t rows, uint32_t len);
 int launch_reduce(gsdr_acq* a, const AcqParams& ap, bool dwells, uint32_t nblocks, gsdr_acq_result* res,
     const uint32_t* prn, uint64_t stamp0, uint64_t stride, hipStream_t s);
 int launch_decide(gsdr_acq* a, uint32_t n, gsdr_acq_result* res, hipStream_t s);
@@ -276,6 +294,10 @@ int fine_prepare(gsdr_acq* a);
 void fine_free(gsdr_acq* a);
 // acq_pair.hip: free the pair buffers
 void pairs_free(gsdr_acq* a);
+// acq_quicksync.hip: the wipe-off rows over an item for the grid in effect (no-op unless
+// configured), free the QuickSync buffers
+int quicksync_rebuild_wipeoffs(gsdr_acq* a);
+void quicksync_free(gsdr_acq* a);
 // acq.hip: the per-plan dispatch of an op, and the code spectra (with their lane-order
 // copies) of slots [first_slot, first_slot + nslots) from their staged codes
 int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op);

@@ -4,6 +4,7 @@
 #pragma once
 #include "acq_handle.h"
 #include "acq_plans.h"
+#include "acq_quicksync_kernels.h"
 
 namespace
 {
@@ -22,6 +23,11 @@ int set_lds_attrs(size_t bytes)
         rc |= with_item_type(it, [&](auto t) {
             return set_max_lds((const void*)acq_forward_kernel<PT, decltype(t)::value>, bytes);
         });
+    if constexpr (!std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
+        for (int it : kItemTypes)
+            rc |= with_item_type(it, [&](auto t) {
+                return set_max_lds((const void*)acq_forward_fold_kernel<PT, decltype(t)::value>, bytes);
+            });
     if constexpr (std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
         {
             rc |= set_max_lds((const void*)acq_argmax_four_kernel<PT>, bytes);
@@ -45,6 +51,18 @@ const typename PT::PlanT& plan_of(const gsdr_acq* a)
 template <class PT>
 void launch_forward(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, hipStream_t s)
 {
+    // a QuickSync run (LDS plans only, acq_quicksync.hip): items of p^2 N samples at stride,
+    // v.wipe their rows, folded by the load
+    if constexpr (!std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
+        if (a->qs.running)
+            {
+                with_item_type(a->conf.item_type, [&](auto t) {
+                    hipLaunchKernelGGL((acq_forward_fold_kernel<PT, decltype(t)::value>), dim3(nblocks, v.xm.q),
+                        dim3(PT::NT), a->lds_bytes, s, iq, stride, v.wipe, a->d_X, a->d_tw, plan_of<PT>(a),
+                        a->qs.p * a->qs.p, v.xm);
+                });
+                return;
+            }
     with_item_type(a->conf.item_type, [&](auto t) {
         hipLaunchKernelGGL((acq_forward_kernel<PT, decltype(t)::value>), dim3(nblocks, v.xm.q), dim3(PT::NT),
             a->lds_bytes, s, iq, stride, v.wipe, a->d_X, a->d_tw, plan_of<PT>(a), a->consumed, v.xm);

@@ -140,6 +140,7 @@ int gsdr_acq_set_code_pairs(gsdr_acq* a, int kind, const float* first, const flo
     GSDR_HIP(hipStreamSynchronize(a->stream));  // ids is read until here
     a->nprn = 2 * npairs;
     a->pairs.npairs = npairs;
+    a->qs.ncodes = 0;
     return GSDR_OK;
 }
 

@@ -3,6 +3,7 @@
 // gsdr_acq::corr_variant.
 #include "acq_handle.h"
 #include "acq_plans.h"
+#include "acq_quicksync_kernels.h"
 #include "acq_split_kernels.h"
 
 namespace gsdr_acq_impl
@@ -147,9 +148,14 @@ int launch_forward_pk(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nb
 {
     return with_pk_variant(a->corr_variant, [&](auto e) {
         using M = typename decltype(e)::type;
+        // a QuickSync run (acq_quicksync.hip): the folding load over items of p^2 N samples
         with_item_type(a->conf.item_type, [&](auto t) {
-            hipLaunchKernelGGL((acq_forward_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q), dim3(M::NT),
-                M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->consumed, v.xm);
+            if (a->qs.running)
+                hipLaunchKernelGGL((acq_forward_fold_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q),
+                    dim3(M::NT), M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->qs.p * a->qs.p, v.xm);
+            else
+                hipLaunchKernelGGL((acq_forward_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q), dim3(M::NT),
+                    M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->consumed, v.xm);
         });
         GSDR_HIP(hipGetLastError());
         return GSDR_OK;
@@ -179,7 +185,8 @@ int setup_corr_variant(gsdr_acq* a, int id)
         rc |= set_max_lds((const void*)acq_argmax_pk_kernel<M, V::STAT, V::PEAK>, a->corr_lds_bytes);
         for (int it : kItemTypes)
             rc |= with_item_type(it, [&](auto t) {
-                return set_max_lds((const void*)acq_forward_pk_kernel<M, decltype(t)::value>, M::lds_bytes());
+                return set_max_lds((const void*)acq_forward_pk_kernel<M, decltype(t)::value>, M::lds_bytes()) |
+                       set_max_lds((const void*)acq_forward_fold_pk_kernel<M, decltype(t)::value>, M::lds_bytes());
             });
         if constexpr (!std::is_void<typename V::Reg>::value)
             rc |= set_max_lds((const void*)acq_correlate_reg_kernel<typename V::Reg>, V::Reg::lds_bytes());

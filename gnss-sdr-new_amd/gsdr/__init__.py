@@ -55,6 +55,8 @@ EXPORTED = [
     "gsdr_acq_fine_doppler", "gsdr_acq_fine_doppler_stream", "gsdr_acq_dump_fine_spectrum", "gsdr_acq_get_fine_plan",
     "gsdr_acq_get_fine_ready",
     "gsdr_acq_set_code_pairs", "gsdr_acq_run_pairs", "gsdr_acq_run_pairs_stream", "gsdr_acq_dump_pair_rows",
+    "gsdr_acq_set_quicksync", "gsdr_acq_set_quicksync_codes", "gsdr_acq_run_quicksync",
+    "gsdr_acq_run_quicksync_stream", "gsdr_acq_dump_quicksync",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -255,6 +257,34 @@ assert all(ACQ_PAIR_RESULT_DTYPE.fields[f][1] == getattr(AcqPairResult, f).offse
 PAIR_AS_IS, PAIR_SUM_DIFF_J = 0, 1
 
 
+class AcqQuickSyncResult(ctypes.Structure):
+    """gsdr_acq_quicksync_result: one (item, PRN) outcome of gsdr_acq_run_quicksync."""
+    _fields_ = [
+        ("prn", ctypes.c_uint32),
+        ("doppler_index", ctypes.c_uint32),
+        ("folded_phase", ctypes.c_uint32),
+        ("candidate", ctypes.c_uint32),
+        ("doppler_hz", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+        ("mag", ctypes.c_float),
+        ("input_power", ctypes.c_float),
+        ("test_statistic", ctypes.c_float),
+        ("candidate_power", ctypes.c_float),
+        ("acq_delay_samples", ctypes.c_double),
+        ("samplestamp", ctypes.c_uint64),
+    ]
+
+
+ACQ_QUICKSYNC_RESULT_DTYPE = np.dtype([
+    ("prn", np.uint32), ("doppler_index", np.uint32), ("folded_phase", np.uint32), ("candidate", np.uint32),
+    ("doppler_hz", np.int32), ("pad", np.int32), ("mag", np.float32), ("input_power", np.float32),
+    ("test_statistic", np.float32), ("candidate_power", np.float32), ("acq_delay_samples", np.float64),
+    ("samplestamp", np.uint64)])
+assert ACQ_QUICKSYNC_RESULT_DTYPE.itemsize == ctypes.sizeof(AcqQuickSyncResult)
+assert all(ACQ_QUICKSYNC_RESULT_DTYPE.fields[f][1] == getattr(AcqQuickSyncResult, f).offset
+           for f, _ in AcqQuickSyncResult._fields_)
+
+
 class CorrJob(ctypes.Structure):
     _fields_ = [
         ("channel", ctypes.c_int32),
@@ -322,6 +352,12 @@ def load():
         L.gsdr_acq_run_pairs.argtypes = [P, P, U32, U64, P]
         L.gsdr_acq_run_pairs_stream.argtypes = [P, P, U64, U32, U64, P]
         L.gsdr_acq_dump_pair_rows.argtypes = [P, P, P]
+    if hasattr(L, "gsdr_acq_set_quicksync"):  # (as above)
+        L.gsdr_acq_set_quicksync.argtypes = [P, U32, U32]
+        L.gsdr_acq_set_quicksync_codes.argtypes = [P, P, P, U32]
+        L.gsdr_acq_run_quicksync.argtypes = [P, P, U32, U64, P]
+        L.gsdr_acq_run_quicksync_stream.argtypes = [P, P, U64, U32, U64, P]
+        L.gsdr_acq_dump_quicksync.argtypes = [P, P, P, P]
     L.gsdr_corr_create.argtypes = [I, I, I, I, P]
     L.gsdr_corr_destroy.argtypes = [P]
     L.gsdr_corr_destroy.restype = None
@@ -763,6 +799,91 @@ class Acquisition:
         m = np.zeros((self.num_doppler_bins, max(npairs, 1), 2), np.float32)
         _check(load().gsdr_acq_dump_pair_rows(self._h, _ptr(iq), _ptr(m)))
         return m
+
+
+    # ---- QuickSync (pcps_quicksync_acquisition_cc)
+    def set_quicksync(self, folding_factor, samples_per_code):
+        """gsdr_acq_set_quicksync: the handle (fft_size = samples_per_code / folding_factor)
+        serves items of folding_factor * samples_per_code samples from now on."""
+        _check(load().gsdr_acq_set_quicksync(self._h, int(folding_factor), int(samples_per_code)))
+        self.folding_factor, self.qs_spc = int(folding_factor), int(samples_per_code)
+
+    def set_quicksync_codes(self, codes, prns):
+        """gsdr_acq_set_quicksync_codes: codes = [nprn, samples_per_code] complex64, unfolded."""
+        codes = np.ascontiguousarray(codes, np.complex64)
+        prns = np.ascontiguousarray(prns, np.uint32)
+        assert codes.ndim == 2 and codes.shape == (len(prns), getattr(self, "qs_spc", codes.shape[1])), codes.shape
+        _check(load().gsdr_acq_set_quicksync_codes(self._h, _ptr(codes), _ptr(prns), len(prns)))
+        self.nprn = len(prns)
+
+    def _quicksync_item(self):
+        return getattr(self, "folding_factor", 0) * getattr(self, "qs_spc", 0)
+
+    def run_quicksync(self, iq, nitems=1, stamp0=0):
+        """gsdr_acq_run_quicksync: nitems host items of folding_factor * samples_per_code
+        samples, each a grid of its own -> structured array [nitems, nprn]
+        (ACQ_QUICKSYNC_RESULT_DTYPE); quicksync_decide applies the dwell rule."""
+        iq = self._items(iq)
+        need = nitems * self._quicksync_item() * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        out = np.zeros(nitems * max(self.nprn, 1), ACQ_QUICKSYNC_RESULT_DTYPE)
+        _check(load().gsdr_acq_run_quicksync(self._h, _ptr(iq), int(nitems), int(stamp0), _ptr(out)))
+        return out.reshape(nitems, -1)
+
+    def run_quicksync_stream(self, ring, first_sample, nitems=1, stamp0=0):
+        """gsdr_acq_run_quicksync_stream: the same on a Stream's items from first_sample."""
+        out = np.zeros(nitems * max(self.nprn, 1), ACQ_QUICKSYNC_RESULT_DTYPE)
+        _check(load().gsdr_acq_run_quicksync_stream(self._h, ring._h, int(first_sample), int(nitems), int(stamp0),
+                                                    _ptr(out)))
+        return out.reshape(nitems, -1)
+
+    def dump_quicksync(self, iq):
+        """gsdr_acq_dump_quicksync of one item -> (normalised row maxima float32
+        [num_doppler_bins, nprn], the winner's candidate powers float32 [nprn, folding_factor])."""
+        iq = self._items(iq)
+        need = self._quicksync_item() * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        rows = np.zeros((self.num_doppler_bins, max(self.nprn, 1)), np.float32)
+        cand = np.zeros((max(self.nprn, 1), max(getattr(self, "folding_factor", 0), 1)), np.float32)
+        _check(load().gsdr_acq_dump_quicksync(self._h, _ptr(iq), _ptr(rows), _ptr(cand)))
+        return rows, cand
+
+
+def quicksync_decide(records, threshold, bit_transition, max_dwells):
+    """The dwell rule of pcps_quicksync_acquisition_cc (:443-467) on one satellite's records,
+    one per dwell in order (a column of run_quicksync) -> (record, positive, num_dwells).
+
+    Every dwell is a grid of its own (d_mag, d_input_power and d_test_statistics are zeroed in
+    every state-1 call, :288-291), so the statistic of dwell k is that record's.  Without bit
+    transition: positive at the first dwell above the threshold, negative at max_dwells.  With
+    it (the adapter passes max_dwells = 2) only the dwell that reaches max_dwells decides, on
+    its own statistic.  positive is None when the records end before the block decides."""
+    records = np.asarray(records)
+    assert records.dtype == ACQ_QUICKSYNC_RESULT_DTYPE and records.ndim == 1 and len(records) > 0
+    thr = np.float32(threshold)
+    for k in range(len(records)):
+        rec = records[k].copy()
+        above = bool(np.float32(rec["test_statistic"]) > thr)
+        if not bit_transition:
+            if above:
+                return rec, True, k + 1
+            if k + 1 == int(max_dwells):
+                return rec, False, k + 1
+        elif k + 1 == int(max_dwells):
+            return rec, above, k + 1
+    return rec, None, len(records)
+
+
+def quicksync_threshold(pfa, samples_per_code, folding_factor, doppler_max, doppler_step):
+    """GpsL1CaPcpsQuickSyncAcquisition::calculate_threshold (adapter :264-281): the quantile of an
+    exponential distribution with lambda = spc / p at (1 - pfa)^(1 / ncells), ncells =
+    (spc / p) * rows, pfa a float, the result cast to float."""
+    assert int(doppler_step) > 0, "the reference's loop over the Doppler rows never ends with doppler_step 0"
+    rows = len(range(-int(doppler_max), int(doppler_max) + 1, int(doppler_step)))
+    ncells = (int(samples_per_code) // int(folding_factor)) * rows
+    val = (1.0 - float(np.float32(pfa))) ** (1.0 / float(ncells))
+    lam = float(samples_per_code) / float(folding_factor)
+    return float(np.float32(-np.log1p(-val) / lam))
 
 
 def pair_decide(records, threshold, carry_mag):

@@ -6,6 +6,7 @@
 #include "gnss_tracking_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_mi355x.h"
+#include "gps_l1_ca_pcps_quicksync_acquisition_mi355x.h"
 #include "gsdr.h"
 
 namespace gsdr_factory
@@ -30,6 +31,9 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
         return std::make_unique<GpsL1CaPcpsAcquisitionMI355X>(configuration, role, in_streams, out_streams, device);
     if (implementation == "GPS_L1_CA_PCPS_Acquisition_Fine_Doppler_MI355X")
         return std::make_unique<GpsL1CaPcpsAcquisitionFineDopplerMI355X>(configuration, role, in_streams, out_streams,
+            device);
+    if (implementation == "GPS_L1_CA_PCPS_QuickSync_Acquisition_MI355X")
+        return std::make_unique<GpsL1CaPcpsQuickSyncAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);
     if (implementation == "Galileo_E1_PCPS_Ambiguous_Acquisition_MI355X")
         return std::make_unique<GalileoE1PcpsAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,

@@ -560,6 +560,65 @@ int gsdr_acq_run_pairs_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first
  * block, out [num_doppler_bins][npairs][2] normalised row maxima, on every FFT plan. */
 int gsdr_acq_dump_pair_rows(gsdr_acq* acq, const void* iq_host, float* out);
 
+/* ---- QuickSync acquisition: pcps_quicksync_acquisition_cc.  With folding factor p and spc
+ * samples per code, an item is L = p spc samples.  Every Doppler row multiplies the whole
+ * item by the row's wipe-off of L samples, folds the product into Nf = spc / p points (the
+ * sum of its p^2 segments, :336-343), and correlates the fold with the code folded the same
+ * way (the sum of its p segments, :146-151) on an Nf-point transform.  The answer of the grid
+ * is the first row, scanning upwards with strict '<' (:370), that holds the grid maximum and
+ * the first index in it; the p delays index + i Nf it stands for are then told apart by p
+ * correlations in time over spc samples of the wiped-off item with the unfolded code, not
+ * conjugated (:383-412): the first maximum of their |.|^2 names the delay.  The handle is an
+ * ordinary one created with consumed_samples == fft_size == Nf, max_dwells 1 and no
+ * bit_transition_flag; the grid runs on its forward, correlate and reduce kernels, whatever
+ * its pfa.  Every item of a call is a grid of its own (the block zeroes d_mag, d_input_power
+ * and d_test_statistics in every state-1 call, :288-291); the dwell rule over the items'
+ * records is the caller's. */
+typedef struct gsdr_acq_quicksync_result
+{
+    uint32_t prn;
+    uint32_t doppler_index;   /* first row holding the grid maximum */
+    uint32_t folded_phase;    /* indext, < Nf */
+    uint32_t candidate;       /* i: the delay is folded_phase + i Nf */
+    int32_t doppler_hz;       /* Acq_doppler_hz */
+    int32_t pad;
+    float mag;                /* d_mag: the maximum / (float(Nf) float(Nf))^2, in float (:286, :367) */
+    float input_power;        /* d_input_power: sum |x|^2 / L of the item (:310-312) */
+    float test_statistic;     /* mag / input_power (:421) */
+    float candidate_power;    /* |acc_i|^2 of the winning delay, as summed (:411) */
+    double acq_delay_samples; /* folded_phase + candidate Nf (:415) */
+    uint64_t samplestamp;     /* the item's first sample: stamp0 + b L */
+} gsdr_acq_quicksync_result;
+
+/* Makes the handle a QuickSync one for folding factor p and samples_per_code spc, and
+ * allocates what the runs need (items of p spc samples for max_blocks items, the wipe-off
+ * rows over an item, max_prns unfolded codes).  GSDR_E_ARG unless 2 <= p <= 16, spc % p == 0
+ * and spc / p == the handle's fft_size.  GSDR_E_UNSUPPORTED for a handle with max_dwells > 1,
+ * bit_transition_flag or consumed_samples != fft_size, and for an fft_size served by the
+ * four-step plans (the fold needs a transform of one launch).  An error leaves the handle as
+ * it was; plain runs on the handle are unaffected by a success too. */
+int gsdr_acq_set_quicksync(gsdr_acq* acq, uint32_t folding_factor, uint32_t samples_per_code);
+/* nprn unfolded replicas of samples_per_code complex<float> each, prn their ids: kept for the
+ * candidate check, folded into code slots 0..nprn-1 and transformed as
+ * gsdr_acq_set_local_codes transforms its rows.  The handle holds QuickSync codes until
+ * gsdr_acq_set_local_codes, gsdr_acq_set_local_code, gsdr_acq_set_active_prns or
+ * gsdr_acq_set_code_pairs is called.  GSDR_E_STATE before gsdr_acq_set_quicksync. */
+int gsdr_acq_set_quicksync_codes(gsdr_acq* acq, const float* codes, const uint32_t* prn, uint32_t nprn);
+/* nitems items of p spc host samples of the handle's item type, out [nitems][nprn] records.
+ * Synchronous.  GSDR_E_STATE before both set calls; GSDR_E_UNSUPPORTED while the handle's
+ * carrier model is not GSDR_WIPE_EXACT; nitems outside [1, max_blocks] is GSDR_E_ARG.  With
+ * gsdr_acq_set_profiling enabled the input-power and candidate kernels are recorded in
+ * stage [2]. */
+int gsdr_acq_run_quicksync(gsdr_acq* acq, const void* iq_host, uint32_t nitems, uint64_t stamp0,
+    gsdr_acq_quicksync_result* out);
+/* The same on the ring's samples from first_sample, read in place. */
+int gsdr_acq_run_quicksync_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_sample, uint32_t nitems,
+    uint64_t stamp0, gsdr_acq_quicksync_result* out_host);
+/* Debug/verification, one item: rows_out [num_doppler_bins][nprn] the normalised row maxima
+ * (magt of every row, :367), cand_out [nprn][p] the |acc_i|^2 of the winner's p delays.
+ * Either output may be null. */
+int gsdr_acq_dump_quicksync(gsdr_acq* acq, const void* iq_host, float* rows_out, float* cand_out);
+
 /* ======================================================================== */
 /* Tracking multicorrelator (Cpu_Multicorrelator_Real_Codes / Cpu_Multicorrelator) */
 /* ======================================================================== */
