@@ -70,21 +70,9 @@ int run_blocks(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, 
 // The same on the ring's samples from first_sample, into d_res on the handle's stream.
 int run_ring(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0)
 {
-    gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-    const void* iq = nullptr;
-    int rc = rd.view(first_sample, (uint64_t)nblocks * a->K * a->consumed, &iq);
-    if (rc == GSDR_OK) rc = rd.acquire(a->stream);
-    if (rc == GSDR_OK) rc = run_blocks(a, view_of(a), iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
-    if (rc == GSDR_OK) rc = rd.release(a->stream);
-    return rc;
-}
-
-// The first n records of d_res to the host, once the handle's stream has produced them.
-int read_results(gsdr_acq* a, gsdr_acq_result* out, size_t n)
-{
-    GSDR_HIP(hipMemcpyAsync(out, a->d_res, n * sizeof(gsdr_acq_result), hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    return with_ring_items(a, ring, first_sample, (uint64_t)nblocks * a->K * a->consumed, [&](const void* iq) {
+        return run_blocks(a, view_of(a), iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
+    });
 }
 
 // update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:307-314), float arithmetic:
@@ -254,7 +242,7 @@ int gsdr_acq_create(int device, const gsdr_acq_conf* conf, gsdr_acq** out)
     if (e == hipSuccess) e = hipMalloc(&a->d_iq, nB * a->K * a->consumed * gsdr::item_bytes(conf->item_type));
     if (a->general)
         {
-            // accumulation rows held by running workgroups only: the chip's resident
+            // accumulation rows held by resident workgroups only: the chip's resident
             // workgroup count bounds the pool
             const int nslots = 256 * 32 / (a->nt / 64);
             a->acc_words = (nslots + 31) / 32;
@@ -380,9 +368,7 @@ int gsdr_acq_set_local_codes(gsdr_acq* a, const float* codes, const uint32_t* pr
     int rc = code_fft(a, 0, nprn);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
-    a->nprn = nprn;
-    a->pairs.npairs = 0;
-    a->qs.ncodes = 0;
+    set_slots(a, gsdr_acq::Slots::Plain, nprn);
     return GSDR_OK;
 }
 
@@ -401,9 +387,7 @@ int gsdr_acq_set_local_code(gsdr_acq* a, uint32_t slot, const float* code, uint3
     int rc = code_fft(a, slot, 1);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));
-    if (a->nprn <= slot) a->nprn = slot + 1;
-    a->pairs.npairs = 0;
-    a->qs.ncodes = 0;
+    set_slots(a, gsdr_acq::Slots::Plain, std::max(a->nprn, slot + 1));
     return GSDR_OK;
 }
 
@@ -413,9 +397,7 @@ int gsdr_acq_set_active_prns(gsdr_acq* a, uint32_t nprn)
     GSDR_REQUIRE(nprn > 0 && nprn <= a->conf.max_prns, GSDR_E_ARG, "gsdr_acq_set_active_prns: %u outside [1,%u]", nprn,
         a->conf.max_prns);
     std::lock_guard<std::mutex> lk(a->mu);
-    a->nprn = nprn;
-    a->pairs.npairs = 0;
-    a->qs.ncodes = 0;
+    set_slots(a, gsdr_acq::Slots::Plain, nprn);
     return GSDR_OK;
 }
 
@@ -475,8 +457,8 @@ int gsdr_acq_run_device(gsdr_acq* a, const void* iq_dev, uint32_t nblocks, uint6
 {
     GSDR_REQUIRE(a && iq_dev && out_dev, GSDR_E_ARG, "gsdr_acq_run_device: null argument");
     GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_device: set_local_codes first");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG, "gsdr_acq_run_device: nblocks %u outside [1,%u]",
-        nblocks, a->conf.max_blocks);
+    int rc = check_block_count(a, "gsdr_acq_run_device", nblocks, "nblocks");
+    if (rc != GSDR_OK) return rc;
     GSDR_REQUIRE(stride >= a->consumed || nblocks == 1, GSDR_E_ARG, "gsdr_acq_run_device: block stride %llu < consumed %u",
         (unsigned long long)stride, a->consumed);
     std::lock_guard<std::mutex> lk(a->mu);
@@ -489,15 +471,15 @@ int gsdr_acq_run(gsdr_acq* a, const void* iq_host, uint32_t nblocks, uint64_t st
 {
     GSDR_REQUIRE(a && iq_host && out, GSDR_E_ARG, "gsdr_acq_run: null argument");
     GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run: set_local_codes first");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG, "gsdr_acq_run: nblocks %u outside [1,%u]",
-        nblocks, a->conf.max_blocks);
+    int rc = check_block_count(a, "gsdr_acq_run", nblocks, "nblocks");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     const size_t bytes = (size_t)nblocks * a->K * a->consumed * gsdr::item_bytes(a->conf.item_type);
     GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, bytes, hipMemcpyHostToDevice, a->stream));
-    int rc = run_blocks(a, view_of(a), a->d_iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
+    rc = run_blocks(a, view_of(a), a->d_iq, nblocks, a->consumed, stamp0, a->d_res, a->stream);
     if (rc != GSDR_OK) return rc;
-    return read_results(a, out, (size_t)nblocks * a->nprn);
+    return read_back(a, out, a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result));
 }
 
 int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0,
@@ -505,31 +487,23 @@ int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, u
 {
     GSDR_REQUIRE(a && ring && out, GSDR_E_ARG, "gsdr_acq_run_stream: null argument");
     GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_stream: set_local_codes first");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG,
-        "gsdr_acq_run_stream: nblocks %u outside [1,%u]", nblocks, a->conf.max_blocks);
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == a->conf.item_type, GSDR_E_ARG,
-        "gsdr_acq_run_stream: ring item type %d != acquisition item type %d", gsdr::stream_item_type(ring),
-        a->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == a->device, GSDR_E_ARG,
-        "gsdr_acq_run_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring), a->device);
+    int rc = check_block_count(a, "gsdr_acq_run_stream", nblocks, "nblocks");
+    if (rc == GSDR_OK) rc = gsdr::check_ring_consumer("gsdr_acq_run_stream", ring, a->conf.item_type, a->device, "acquisition");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
-    int rc = run_ring(a, ring, first_sample, nblocks, stamp0);
+    rc = run_ring(a, ring, first_sample, nblocks, stamp0);
     if (rc != GSDR_OK) return rc;
-    return read_results(a, out, (size_t)nblocks * a->nprn);
+    return read_back(a, out, a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result));
 }
 
 int gsdr_acq_submit_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0)
 {
     GSDR_REQUIRE(a && ring, GSDR_E_ARG, "gsdr_acq_submit_stream: null argument");
     GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_submit_stream: set_local_codes first");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG,
-        "gsdr_acq_submit_stream: nblocks %u outside [1,%u]", nblocks, a->conf.max_blocks);
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == a->conf.item_type, GSDR_E_ARG,
-        "gsdr_acq_submit_stream: ring item type %d != acquisition item type %d", gsdr::stream_item_type(ring),
-        a->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == a->device, GSDR_E_ARG,
-        "gsdr_acq_submit_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring), a->device);
+    int rc = check_block_count(a, "gsdr_acq_submit_stream", nblocks, "nblocks");
+    if (rc == GSDR_OK) rc = gsdr::check_ring_consumer("gsdr_acq_submit_stream", ring, a->conf.item_type, a->device, "acquisition");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
     GSDR_REQUIRE(a->sub_count < gsdr_acq::kSubs, GSDR_E_STATE,
         "gsdr_acq_submit_stream: %d submissions in flight, collect the oldest first", gsdr_acq::kSubs);
@@ -541,7 +515,7 @@ int gsdr_acq_submit_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample
                 (size_t)a->conf.max_blocks * a->conf.max_prns * sizeof(gsdr_acq_result), hipHostMallocDefault));
             GSDR_HIP(hipEventCreateWithFlags(&a->sub_done[slot], hipEventDisableTiming));
         }
-    int rc = run_ring(a, ring, first_sample, nblocks, stamp0);
+    rc = run_ring(a, ring, first_sample, nblocks, stamp0);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipMemcpyAsync(a->h_res[slot], a->d_res, (size_t)nblocks * a->nprn * sizeof(gsdr_acq_result),
         hipMemcpyDeviceToHost, a->stream));
@@ -587,7 +561,7 @@ int gsdr_acq_run_dwell(gsdr_acq* a, const void* iq_host, uint32_t dwell, uint64_
     op.s = a->stream;
     int rc = dispatch(a, view_of(a), op);
     if (rc != GSDR_OK) return rc;
-    return read_results(a, out, a->nprn);
+    return read_back(a, out, a->d_res, a->nprn * sizeof(gsdr_acq_result));
 }
 
 int gsdr_acq_dump_spectra(gsdr_acq* a, const void* iq_host, float* spectra_host)
@@ -640,13 +614,7 @@ int gsdr_acq_dump_row_maxima(gsdr_acq* a, const void* iq_host, float* out_host)
     if (rc == GSDR_OK) rc = launch_corr_variant(a, v, 1, a->stream);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipGetLastError());
-    // stats[p D + d] of block 0
-    std::vector<RowStat> st((size_t)v.nprn * v.D);
-    GSDR_HIP(hipMemcpyAsync(st.data(), a->d_stats, st.size() * sizeof(RowStat), hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    for (uint32_t d = 0; d < v.D; ++d)
-        for (uint32_t p = 0; p < v.nprn; ++p) out_host[(size_t)d * v.nprn + p] = st[(size_t)p * v.D + d].max;
-    return GSDR_OK;
+    return row_maxima_to_host(a, v.nprn, v.D, 1.0f, out_host);
 }
 
 int gsdr_acq_dump_grid_step_two(gsdr_acq* a, const void* iq_host, uint32_t prn_slot, float doppler_center_hz,
@@ -742,12 +710,22 @@ int gsdr_acq_run_step_two(gsdr_acq* a, const void* iq_host, uint32_t nsel, const
     const float thr = step_two_threshold(a);
     for (uint32_t i = 0; i < nsel && rc == GSDR_OK; ++i)
         {
-            const AcqView v{nb, 1, a->st2.d_wipe + (size_t)i * nb * a->N, a->d_code_fft + (size_t)prn_slots[i] * a->N,
-                a->d_code_lane ? a->d_code_lane + (size_t)prn_slots[i] * a->N : nullptr, a->d_prn + prn_slots[i], XMap{nb, 0u, a->N}, true, doppler_center_hz[i], coarse_input_power[i], thr};
+            AcqView v;
+            v.D = nb;
+            v.nprn = 1;
+            v.wipe = a->st2.d_wipe + (size_t)i * nb * a->N;
+            v.code_fft = a->d_code_fft + (size_t)prn_slots[i] * a->N;
+            v.code_lane = a->d_code_lane ? a->d_code_lane + (size_t)prn_slots[i] * a->N : nullptr;
+            v.prn = a->d_prn + prn_slots[i];
+            v.xm = XMap{nb, 0u, a->N};
+            v.step_two = true;
+            v.center2 = doppler_center_hz[i];
+            v.ip2 = coarse_input_power[i];
+            v.threshold2 = thr;
             rc = run_blocks(a, v, a->d_iq, 1, a->consumed, stamp, a->d_res + i, a->stream);
         }
     if (rc != GSDR_OK) return rc;
-    return read_results(a, out, nsel);
+    return read_back(a, out, a->d_res, nsel * sizeof(gsdr_acq_result));
 }
 
 int gsdr_acq_set_cu_mask(gsdr_acq* a, const uint32_t* mask, int n_words)

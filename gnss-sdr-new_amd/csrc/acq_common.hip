@@ -375,7 +375,6 @@ namespace gsdr_acq_impl
 //       plan) or one PRN per 512-lane workgroup (1, the default)
 //   GSDR_ACQ_CORR_VARIANT  a packed correlate variant (PkVariants, acq_pk.hip) other
 //       than default_pk_variant's, for tests
-// (GSDR_ACQ_QS_CAND_LOOP is read by gsdr_acq_set_quicksync, acq_quicksync.hip.)
 AcqEnv read_acq_env()
 {
     AcqEnv e;
@@ -397,7 +396,50 @@ AcqEnv read_acq_env()
 // The main grid's view: every Doppler row and active PRN of the handle.
 AcqView view_of(const gsdr_acq* a)
 {
-    return AcqView{a->D, a->nprn, a->d_wipe, a->d_code_fft, a->d_code_lane, a->d_prn, a->xm, false, 0.0f, 0.0f, 0.0f};
+    AcqView v;
+    v.D = a->D;
+    v.nprn = a->nprn;
+    v.wipe = a->d_wipe;
+    v.code_fft = a->d_code_fft;
+    v.code_lane = a->d_code_lane;
+    v.prn = a->d_prn;
+    v.xm = a->xm;
+    return v;
+}
+
+int check_block_count(const gsdr_acq* a, const char* who, uint32_t n, const char* name)
+{
+    GSDR_REQUIRE(n > 0 && n <= a->conf.max_blocks, GSDR_E_ARG, "%s: %s %u outside [1,%u]", who, name, n,
+        a->conf.max_blocks);
+    return GSDR_OK;
+}
+
+int check_single_grid_handle(const gsdr_acq* a, const char* who, const char* what)
+{
+    GSDR_REQUIRE(!a->conf.bit_transition_flag, GSDR_E_UNSUPPORTED, "%s: no %s with bit_transition_flag", who, what);
+    GSDR_REQUIRE(a->K == 1, GSDR_E_UNSUPPORTED,
+        "%s: %s: every item is a grid of its own; the handle must be created with max_dwells 1 (has %u)", who, what,
+        a->K);
+    GSDR_REQUIRE(a->consumed == a->N, GSDR_E_UNSUPPORTED,
+        "%s: %s: blocks must be fft_size items (consumed_samples %u, fft_size %u)", who, what, a->consumed, a->N);
+    return GSDR_OK;
+}
+
+int read_back(gsdr_acq* a, void* dst_host, const void* src_dev, size_t bytes)
+{
+    GSDR_HIP(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, a->stream));
+    GSDR_HIP(hipStreamSynchronize(a->stream));
+    return GSDR_OK;
+}
+
+int row_maxima_to_host(gsdr_acq* a, uint32_t P, uint32_t D, float divisor, float* out)
+{
+    std::vector<RowStat> st((size_t)P * D);
+    const int rc = read_back(a, st.data(), a->d_stats, st.size() * sizeof(RowStat));
+    if (rc != GSDR_OK) return rc;
+    for (uint32_t d = 0; d < D; ++d)
+        for (uint32_t p = 0; p < P; ++p) out[(size_t)d * P + p] = st[(size_t)p * D + d].max / divisor;
+    return GSDR_OK;
 }
 
 AcqParams params_of(const gsdr_acq* a, const AcqView& v)
@@ -416,9 +458,7 @@ AcqParams params_of(const gsdr_acq* a, const AcqView& v)
     ap.samples_per_chip = a->conf.samples_per_chip;
     ap.dwells = a->K;
     ap.threshold = a->threshold;
-    // a pair run reads no second peak: its launches are the CFAR sequence's (acq_pair.hip)
-    // (nor does a QuickSync run, acq_quicksync.hip)
-    ap.cfar = (a->conf.pfa > 0.0f || a->pairs.running || a->qs.running) ? 1 : 0;
+    ap.cfar = (a->conf.pfa > 0.0f || v.first_peak_only) ? 1 : 0;
     ap.eff = a->eff;
     ap.out_off = a->N - a->eff;
     ap.counter = a->K;

@@ -225,14 +225,6 @@ int check_requests(const gsdr_acq* a, const char* who, const gsdr_acq_fine_reque
     return GSDR_OK;
 }
 
-int read_fine_results(gsdr_acq* a, gsdr_acq_fine_result* out, uint32_t nreq)
-{
-    GSDR_HIP(hipMemcpyAsync(out, a->fine.d_out, (size_t)nreq * sizeof(gsdr_acq_fine_result), hipMemcpyDeviceToHost,
-        a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
-}
-
 }  // namespace
 
 int gsdr_acq_impl::fine_prepare(gsdr_acq* a)
@@ -307,7 +299,7 @@ int gsdr_acq_fine_doppler(gsdr_acq* a, const void* iq_host, const float* codes, 
         hipMemcpyHostToDevice, a->stream));
     rc = fine_enqueue(a, a->fine.d_iq, codes, ncodes, requests, nreq, nullptr);
     if (rc != GSDR_OK) return rc;
-    return read_fine_results(a, out, nreq);
+    return read_back(a, out, a->fine.d_out, (size_t)nreq * sizeof(gsdr_acq_fine_result));
 }
 
 int gsdr_acq_fine_doppler_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, const float* codes,
@@ -316,26 +308,17 @@ int gsdr_acq_fine_doppler_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_
     GSDR_REQUIRE(a && ring && codes && requests && out_host, GSDR_E_ARG, "gsdr_acq_fine_doppler_stream: null argument");
     int rc = check_requests(a, "gsdr_acq_fine_doppler_stream", requests, nreq, ncodes);
     if (rc != GSDR_OK) return rc;
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == a->conf.item_type, GSDR_E_ARG,
-        "gsdr_acq_fine_doppler_stream: ring item type %d != acquisition item type %d", gsdr::stream_item_type(ring),
-        a->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == a->device, GSDR_E_ARG,
-        "gsdr_acq_fine_doppler_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring),
-        a->device);
+    rc = gsdr::check_ring_consumer("gsdr_acq_fine_doppler_stream", ring, a->conf.item_type, a->device, "acquisition");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
     rc = fine_prepare(a);
     if (rc != GSDR_OK) return rc;
-    {
-        gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-        const void* iq = nullptr;
-        rc = rd.view(first_sample, (uint64_t)a->fine.L, &iq);
-        if (rc == GSDR_OK) rc = rd.acquire(a->stream);
-        if (rc == GSDR_OK) rc = fine_enqueue(a, iq, codes, ncodes, requests, nreq, nullptr);
-        if (rc == GSDR_OK) rc = rd.release(a->stream);
-    }
+    rc = with_ring_items(a, ring, first_sample, a->fine.L, [&](const void* iq) {
+        return fine_enqueue(a, iq, codes, ncodes, requests, nreq, nullptr);
+    });
     if (rc != GSDR_OK) return rc;
-    return read_fine_results(a, out_host, nreq);
+    return read_back(a, out_host, a->fine.d_out, (size_t)nreq * sizeof(gsdr_acq_fine_result));
 }
 
 int gsdr_acq_dump_fine_spectrum(gsdr_acq* a, const void* iq_host, const float* code, uint32_t code_phase,
@@ -356,9 +339,7 @@ int gsdr_acq_dump_fine_spectrum(gsdr_acq* a, const void* iq_host, const float* c
         a->stream));
     rc = fine_enqueue(a, f.d_iq, code, 1, &rq, 1, f.d_spec);
     if (rc != GSDR_OK) return rc;
-    GSDR_HIP(hipMemcpyAsync(spectrum_host, f.d_spec, M * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
-    return GSDR_OK;
+    return read_back(a, spectrum_host, f.d_spec, M * sizeof(float));
 }
 
 }  // extern "C"

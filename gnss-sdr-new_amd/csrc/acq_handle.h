@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "acq_kernels.h"
+#include "gsdr_stream_internal.h"
 
 // Runtime switches, read once per handle by read_acq_env (acq_common.hip, which
 // documents each of them).
@@ -54,6 +55,14 @@ struct gsdr_acq
     float2* d_code_stage{nullptr};
     uint32_t* d_prn{nullptr};
     uint32_t nprn{0};
+    // what the nprn active code slots hold (set_slots, called by every code setter):
+    // plain codes, nprn / 2 pairs or nprn folded QuickSync codes
+    enum class Slots
+    {
+        Plain,
+        Pairs,
+        QuickSync
+    } slots{Slots::Plain};
     float2* d_X{nullptr};
     gsdr_acq_impl::RowStat* d_stats{nullptr};
     gsdr_acq_result* d_res{nullptr};
@@ -124,8 +133,6 @@ struct gsdr_acq
     // gsdr_acq_set_code_pairs
     struct Pairs
     {
-        uint32_t npairs{0};       // > 0: the code slots hold pairs
-        bool running{false};      // a pair run's launches: no second-peak pass (params_of)
         float2* d_in{nullptr};    // the caller's two arguments: 2 x (max_prns / 2) rows of N
         float* d_power{nullptr};  // max_blocks input powers
         gsdr_acq_pair_result* d_out{nullptr};  // max_blocks x (max_prns / 2) records
@@ -136,9 +143,6 @@ struct gsdr_acq
     {
         uint32_t p{0};            // folding factor (> 0: configured)
         uint32_t spc{0};          // samples per code (p Nf); an item is L = p spc samples
-        uint32_t ncodes{0};       // > 0: the code slots hold folded QuickSync codes
-        bool running{false};      // a QuickSync run's launches: the folding forward, no second-peak pass
-        bool cand_loop{false};    // GSDR_ACQ_QS_CAND_LOOP=1: one workgroup per (item, slot) over the p candidates
         void* d_iq{nullptr};      // host items' staging: max_blocks x L items of the handle's type
         float2* d_wipe{nullptr};  // D rows (xm.q with the spectrum reuse) of L
         float2* d_codes{nullptr}; // max_prns unfolded codes of spc
@@ -152,20 +156,28 @@ struct gsdr_acq
 namespace gsdr_acq_impl
 {
 
-// What a launch runs on: the Doppler rows, PRNs and spectrum layout in effect.
-// Built from the handle at the top of each ABI call (view_of); step two builds a
-// one-PRN view over its narrow rows instead of altering the handle.
+// What a launch runs on: the Doppler rows, PRNs and spectrum layout in effect, and the
+// mode of the run.  Built from the handle at the top of each ABI call (view_of); step
+// two builds a one-PRN view over its narrow rows, and a pair or QuickSync run sets its
+// mode on its own view, instead of altering the handle.  The launch functions read the
+// mode here, never on the handle.
 struct AcqView
 {
-    uint32_t D, nprn;
-    const float2* wipe;      // D wipe-off rows (xm.q of them with the spectrum reuse)
-    const float2* code_fft;  // nprn code spectra
-    const float2* code_lane; // the same rows in lane order (null unless the handle keeps them)
-    const uint32_t* prn;     // their PRN ids
-    XMap xm;
+    uint32_t D{0}, nprn{0};
+    const float2* wipe{nullptr};      // D wipe-off rows (xm.q of them with the spectrum reuse)
+    const float2* code_fft{nullptr};  // nprn code spectra
+    const float2* code_lane{nullptr}; // the same rows in lane order (null unless the handle keeps them)
+    const uint32_t* prn{nullptr};     // their PRN ids
+    XMap xm{};
     // make_two_steps narrow grid (AcqParams::step_two ...)
-    bool step_two;
-    float center2, ip2, threshold2;
+    bool step_two{false};
+    float center2{0.0f}, ip2{0.0f}, threshold2{0.0f};
+    // > 0: the forward pass folds that many segments per point (QuickSync's p^2, LDS and
+    // packed plans only); the items are op.stride apart and wipe holds rows over an item
+    uint32_t fold_segments{0};
+    // the CFAR launch sequence whatever conf.pfa says: its reduce and selected-row passes
+    // give each slot's maximum, row and first index, and no second-peak pass follows
+    bool first_peak_only{false};
 };
 
 // The operation of a per-plan dispatch, with the arguments each kind reads.
@@ -210,6 +222,13 @@ auto with_item_type(int it, F&& f)
     return f(std::integral_constant<int, GSDR_ITEM_IBYTE>{});
 }
 constexpr int kItemTypes[] = {GSDR_ITEM_GR_COMPLEX, GSDR_ITEM_CSHORT, GSDR_ITEM_IBYTE};
+
+// The one statement of what the code slots hold, for the five code setters.
+inline void set_slots(gsdr_acq* a, gsdr_acq::Slots kind, uint32_t nprn)
+{
+    a->slots = kind;
+    a->nprn = nprn;
+}
 
 inline int set_max_lds(const void* kernel, size_t bytes)
 {
@@ -261,6 +280,19 @@ AcqParams params_of(const gsdr_acq* a, const AcqView& v);
 int rebuild_wipeoffs(gsdr_acq* a);
 void compute_threshold(gsdr_acq* a);
 float step_two_threshold(const gsdr_acq* a);
+// argument and handle checks shared by the ABI calls; `who` names the call in the message:
+// n (called `name`) in [1, max_blocks]; no bit transition, max_dwells 1 and blocks of
+// fft_size items, which the modes that take each item as one grid of its own need
+// (`what`: "pairs", "QuickSync")
+int check_block_count(const gsdr_acq* a, const char* who, uint32_t n, const char* name);
+int check_single_grid_handle(const gsdr_acq* a, const char* who, const char* what);
+// bytes of device memory to the host behind the work enqueued so far on the handle's
+// stream, which is synchronised
+int read_back(gsdr_acq* a, void* dst_host, const void* src_dev, size_t bytes);
+// the row maxima a correlate left in d_stats[p D + d] (block 0), behind the work enqueued
+// so far: out[d P + p] = max / divisor (a division, as the records' normalisation is: the
+// product with the reciprocal rounds differently)
+int row_maxima_to_host(gsdr_acq* a, uint32_t P, uint32_t D, float divisor, float* out);
 // the kernels that are no templates: rows of Doppler wipe-offs (freqs, or the main
 // grid of the handle's configuration when null), the grid maximum and statistic per
 // (block, PRN) or (dwells) per (block, PRN, dwell), the dwell decision, the second peak
@@ -302,5 +334,19 @@ void quicksync_free(gsdr_acq* a);
 // copies) of slots [first_slot, first_slot + nslots) from their staged codes
 int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op);
 int code_fft(gsdr_acq* a, uint32_t first_slot, uint32_t nslots);
+
+// enqueue(iq) on items [first, first + n_items) of the ring, under one hold of the ring's
+// lock from the view to the reader-event record (StreamReader); the first non-OK code.
+template <class Enqueue>
+int with_ring_items(gsdr_acq* a, gsdr_stream* ring, uint64_t first, uint64_t n_items, Enqueue&& enqueue)
+{
+    gsdr::StreamReader rd(ring);
+    const void* iq = nullptr;
+    int rc = rd.view(first, n_items, &iq);
+    if (rc == GSDR_OK) rc = rd.acquire(a->stream);
+    if (rc == GSDR_OK) rc = enqueue(iq);
+    if (rc == GSDR_OK) rc = rd.release(a->stream);
+    return rc;
+}
 
 }  // namespace gsdr_acq_impl

@@ -51,15 +51,15 @@ const typename PT::PlanT& plan_of(const gsdr_acq* a)
 template <class PT>
 void launch_forward(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nblocks, uint64_t stride, hipStream_t s)
 {
-    // a QuickSync run (LDS plans only, acq_quicksync.hip): items of p^2 N samples at stride,
-    // v.wipe their rows, folded by the load
+    // a folding view (LDS plans only; QuickSync, acq_quicksync.hip): items of fold_segments N
+    // samples at stride, v.wipe their rows, folded by the load
     if constexpr (!std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
-        if (a->qs.running)
+        if (v.fold_segments > 0)
             {
                 with_item_type(a->conf.item_type, [&](auto t) {
                     hipLaunchKernelGGL((acq_forward_fold_kernel<PT, decltype(t)::value>), dim3(nblocks, v.xm.q),
                         dim3(PT::NT), a->lds_bytes, s, iq, stride, v.wipe, a->d_X, a->d_tw, plan_of<PT>(a),
-                        a->qs.p * a->qs.p, v.xm);
+                        v.fold_segments, v.xm);
                 });
                 return;
             }

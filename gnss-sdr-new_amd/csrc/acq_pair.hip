@@ -1,7 +1,7 @@
 // Paired-code acquisition: the launch code and C ABI of gsdr_acq_set_code_pairs,
 // gsdr_acq_run_pairs, gsdr_acq_run_pairs_stream and gsdr_acq_dump_pair_rows.  The kernels
 // are in acq_pair_kernels.h; the transforms are the engine's own (the AcqOp::Run
-// sequence over two code slots per pair).
+// sequence over two code slots per pair, on a view marked first_peak_only).
 #include <vector>
 
 #include "acq_handle.h"
@@ -13,22 +13,12 @@ using namespace gsdr_acq_impl;
 namespace
 {
 
-// What a pair call needs of the handle; `who` names the call in the message.
-int check_pair_handle(const gsdr_acq* a, const char* who)
-{
-    GSDR_REQUIRE(!a->conf.bit_transition_flag, GSDR_E_UNSUPPORTED, "%s: no pairs with bit_transition_flag", who);
-    GSDR_REQUIRE(a->K == 1, GSDR_E_UNSUPPORTED,
-        "%s: pairs accumulate no grid over dwells; the handle must be created with max_dwells 1 (has %u)", who, a->K);
-    GSDR_REQUIRE(a->consumed == a->N, GSDR_E_UNSUPPORTED,
-        "%s: pairs need blocks of fft_size items (consumed_samples %u, fft_size %u)", who, a->consumed, a->N);
-    return GSDR_OK;
-}
-
+// What a pair run needs of the handle; `who` names the call in the message.
 int check_pair_run(const gsdr_acq* a, const char* who)
 {
-    const int rc = check_pair_handle(a, who);
+    const int rc = check_single_grid_handle(a, who, "pairs");
     if (rc != GSDR_OK) return rc;
-    GSDR_REQUIRE(a->pairs.npairs > 0, GSDR_E_STATE, "%s: gsdr_acq_set_code_pairs first", who);
+    GSDR_REQUIRE(a->slots == gsdr_acq::Slots::Pairs, GSDR_E_STATE, "%s: gsdr_acq_set_code_pairs first", who);
     return GSDR_OK;
 }
 
@@ -49,24 +39,17 @@ int pairs_prepare(gsdr_acq* a)
     return GSDR_OK;
 }
 
-// While alive the handle's launches are a pair run's (params_of): the CFAR sequence,
-// whose reduce and selected-row passes give each slot's maximum, row and first index
-// and launch no second-peak pass.
-struct PairRun
-{
-    gsdr_acq* a;
-    explicit PairRun(gsdr_acq* a_) : a(a_) { a->pairs.running = true; }
-    ~PairRun() { a->pairs.running = false; }
-};
-
-// nblocks grids over the 2 npairs slots at iq (device), the input powers and the merged
-// records into pairs.d_out, on the handle's stream.
+// nblocks grids over the nprn = 2 npairs slots at iq (device), the input powers and the
+// merged records into pairs.d_out, on the handle's stream.  A pair reads no second peak:
+// the view is first_peak_only.
 int enqueue_pairs(gsdr_acq* a, const void* iq, uint32_t nblocks, uint64_t stamp0)
 {
-    PairRun mark(a);
     hipStream_t s = a->stream;
-    const int rc = dispatch(a, view_of(a), AcqOp{AcqOp::Run, iq, nblocks, a->consumed, stamp0, a->d_res, s});
+    AcqView v = view_of(a);
+    v.first_peak_only = true;
+    const int rc = dispatch(a, v, AcqOp{AcqOp::Run, iq, nblocks, a->consumed, stamp0, a->d_res, s});
     if (rc != GSDR_OK) return rc;
+    const uint32_t npairs = v.nprn / 2;
     StageTimer t(a, s);
     t.begin();
     with_item_type(a->conf.item_type, [&](auto it) {
@@ -74,20 +57,12 @@ int enqueue_pairs(gsdr_acq* a, const void* iq, uint32_t nblocks, uint64_t stamp0
             (uint64_t)a->consumed, a->N, a->pairs.d_power);
     });
     GSDR_HIP(hipGetLastError());
-    const uint32_t n = nblocks * a->pairs.npairs;
+    const uint32_t n = nblocks * npairs;
     hipLaunchKernelGGL(acq_pair_merge_kernel, dim3((n + 63) / 64), dim3(64), 0, s, (const gsdr_acq_result*)a->d_res,
-        (const float*)a->pairs.d_power, a->pairs.d_out, a->pairs.npairs, n, (float)a->N,
+        (const float*)a->pairs.d_power, a->pairs.d_out, npairs, n, (float)a->N,
         (uint32_t)a->conf.samples_per_code);
     GSDR_HIP(hipGetLastError());
     t.end(2);
-    return GSDR_OK;
-}
-
-int read_pair_results(gsdr_acq* a, gsdr_acq_pair_result* out, uint32_t nblocks)
-{
-    GSDR_HIP(hipMemcpyAsync(out, a->pairs.d_out, (size_t)nblocks * a->pairs.npairs * sizeof(gsdr_acq_pair_result),
-        hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
     return GSDR_OK;
 }
 
@@ -115,7 +90,7 @@ int gsdr_acq_set_code_pairs(gsdr_acq* a, int kind, const float* first, const flo
     GSDR_REQUIRE(npairs > 0 && 2ull * npairs <= a->conf.max_prns, GSDR_E_ARG,
         "gsdr_acq_set_code_pairs: %u pairs need %llu code slots, the handle has %u", npairs, 2ull * npairs,
         a->conf.max_prns);
-    int rc = check_pair_handle(a, "gsdr_acq_set_code_pairs");
+    int rc = check_single_grid_handle(a, "gsdr_acq_set_code_pairs", "pairs");
     if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
     gsdr::DeviceGuard g(a->device);
@@ -138,54 +113,42 @@ int gsdr_acq_set_code_pairs(gsdr_acq* a, int kind, const float* first, const flo
     rc = code_fft(a, 0, 2 * npairs);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));  // ids is read until here
-    a->nprn = 2 * npairs;
-    a->pairs.npairs = npairs;
-    a->qs.ncodes = 0;
+    set_slots(a, gsdr_acq::Slots::Pairs, 2 * npairs);
     return GSDR_OK;
 }
 
 int gsdr_acq_run_pairs(gsdr_acq* a, const void* iq_host, uint32_t nblocks, uint64_t stamp0, gsdr_acq_pair_result* out)
 {
     GSDR_REQUIRE(a && iq_host && out, GSDR_E_ARG, "gsdr_acq_run_pairs: null argument");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG, "gsdr_acq_run_pairs: nblocks %u outside [1,%u]",
-        nblocks, a->conf.max_blocks);
+    int rc = check_block_count(a, "gsdr_acq_run_pairs", nblocks, "nblocks");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
-    int rc = check_pair_run(a, "gsdr_acq_run_pairs");
+    rc = check_pair_run(a, "gsdr_acq_run_pairs");
     if (rc != GSDR_OK) return rc;
     gsdr::DeviceGuard g(a->device);
     GSDR_HIP(hipMemcpyAsync(a->d_iq, iq_host, (size_t)nblocks * a->consumed * gsdr::item_bytes(a->conf.item_type),
         hipMemcpyHostToDevice, a->stream));
     rc = enqueue_pairs(a, a->d_iq, nblocks, stamp0);
     if (rc != GSDR_OK) return rc;
-    return read_pair_results(a, out, nblocks);
+    return read_back(a, out, a->pairs.d_out, (size_t)nblocks * (a->nprn / 2) * sizeof(gsdr_acq_pair_result));
 }
 
 int gsdr_acq_run_pairs_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0,
     gsdr_acq_pair_result* out)
 {
     GSDR_REQUIRE(a && ring && out, GSDR_E_ARG, "gsdr_acq_run_pairs_stream: null argument");
-    GSDR_REQUIRE(nblocks > 0 && nblocks <= a->conf.max_blocks, GSDR_E_ARG,
-        "gsdr_acq_run_pairs_stream: nblocks %u outside [1,%u]", nblocks, a->conf.max_blocks);
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == a->conf.item_type, GSDR_E_ARG,
-        "gsdr_acq_run_pairs_stream: ring item type %d != acquisition item type %d", gsdr::stream_item_type(ring),
-        a->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == a->device, GSDR_E_ARG,
-        "gsdr_acq_run_pairs_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring),
-        a->device);
+    int rc = check_block_count(a, "gsdr_acq_run_pairs_stream", nblocks, "nblocks");
+    if (rc == GSDR_OK)
+        rc = gsdr::check_ring_consumer("gsdr_acq_run_pairs_stream", ring, a->conf.item_type, a->device, "acquisition");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
-    int rc = check_pair_run(a, "gsdr_acq_run_pairs_stream");
+    rc = check_pair_run(a, "gsdr_acq_run_pairs_stream");
     if (rc != GSDR_OK) return rc;
     gsdr::DeviceGuard g(a->device);
-    {
-        gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-        const void* iq = nullptr;
-        rc = rd.view(first_sample, (uint64_t)nblocks * a->consumed, &iq);
-        if (rc == GSDR_OK) rc = rd.acquire(a->stream);
-        if (rc == GSDR_OK) rc = enqueue_pairs(a, iq, nblocks, stamp0);
-        if (rc == GSDR_OK) rc = rd.release(a->stream);
-    }
+    rc = with_ring_items(a, ring, first_sample, (uint64_t)nblocks * a->consumed,
+        [&](const void* iq) { return enqueue_pairs(a, iq, nblocks, stamp0); });
     if (rc != GSDR_OK) return rc;
-    return read_pair_results(a, out, nblocks);
+    return read_back(a, out, a->pairs.d_out, (size_t)nblocks * (a->nprn / 2) * sizeof(gsdr_acq_pair_result));
 }
 
 int gsdr_acq_dump_pair_rows(gsdr_acq* a, const void* iq_host, float* out)
@@ -201,14 +164,8 @@ int gsdr_acq_dump_pair_rows(gsdr_acq* a, const void* iq_host, float* out)
     // stats[p D + d]
     rc = enqueue_pairs(a, a->d_iq, 1, 0);
     if (rc != GSDR_OK) return rc;
-    const uint32_t P = a->nprn, D = a->D;
-    std::vector<RowStat> st((size_t)P * D);
-    GSDR_HIP(hipMemcpyAsync(st.data(), a->d_stats, st.size() * sizeof(RowStat), hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
     const float norm = (float)a->N * (float)a->N;
-    for (uint32_t d = 0; d < D; ++d)
-        for (uint32_t p = 0; p < P; ++p) out[(size_t)d * P + p] = st[(size_t)p * D + d].max / (norm * norm);
-    return GSDR_OK;
+    return row_maxima_to_host(a, a->nprn, a->D, norm * norm, out);
 }
 
 }  // extern "C"

@@ -148,11 +148,12 @@ int launch_forward_pk(gsdr_acq* a, const AcqView& v, const void* iq, uint32_t nb
 {
     return with_pk_variant(a->corr_variant, [&](auto e) {
         using M = typename decltype(e)::type;
-        // a QuickSync run (acq_quicksync.hip): the folding load over items of p^2 N samples
+        // a folding view (QuickSync, acq_quicksync.hip): the folding load over items of
+        // fold_segments N samples
         with_item_type(a->conf.item_type, [&](auto t) {
-            if (a->qs.running)
+            if (v.fold_segments > 0)
                 hipLaunchKernelGGL((acq_forward_fold_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q),
-                    dim3(M::NT), M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->qs.p * a->qs.p, v.xm);
+                    dim3(M::NT), M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, v.fold_segments, v.xm);
             else
                 hipLaunchKernelGGL((acq_forward_pk_kernel<M, decltype(t)::value>), dim3(nblocks, v.xm.q), dim3(M::NT),
                     M::lds_bytes(), s, iq, stride, v.wipe, a->d_X, a->d_tw, a->consumed, v.xm);

@@ -1,13 +1,8 @@
 // QuickSync acquisition: the launch code and C ABI of gsdr_acq_set_quicksync,
 // gsdr_acq_set_quicksync_codes, gsdr_acq_run_quicksync, gsdr_acq_run_quicksync_stream and
 // gsdr_acq_dump_quicksync.  The template kernels are in acq_quicksync_kernels.h; the grid
-// is the engine's own (the AcqOp::Run sequence on the handle's Nf-point plan, its forward
-// pass replaced by the folding one while a run is marked).
-//
-// GSDR_ACQ_QS_CAND_LOOP=1 (read by gsdr_acq_set_quicksync): the candidate check as one
-// workgroup per (item, slot) looping over the p delays instead of one workgroup per delay.
-#include <cstdlib>
-#include <vector>
+// is the engine's own (the AcqOp::Run sequence on the handle's Nf-point plan, on a view
+// whose fold_segments = p^2 selects the folding forward pass and that is first_peak_only).
 
 #include "acq_handle.h"
 #include "acq_power_kernel.h"
@@ -79,11 +74,8 @@ __global__ void __launch_bounds__(64) acq_quick_merge_kernel(const gsdr_acq_resu
 // What a QuickSync call needs of the handle; `who` names the call in the message.
 int check_quick_handle(const gsdr_acq* a, const char* who)
 {
-    GSDR_REQUIRE(!a->conf.bit_transition_flag, GSDR_E_UNSUPPORTED, "%s: no QuickSync with bit_transition_flag", who);
-    GSDR_REQUIRE(a->K == 1, GSDR_E_UNSUPPORTED,
-        "%s: every item is a grid of its own; the handle must be created with max_dwells 1 (has %u)", who, a->K);
-    GSDR_REQUIRE(a->consumed == a->N, GSDR_E_UNSUPPORTED,
-        "%s: QuickSync folds into fft_size points (consumed_samples %u, fft_size %u)", who, a->consumed, a->N);
+    const int rc = check_single_grid_handle(a, who, "QuickSync");
+    if (rc != GSDR_OK) return rc;
     GSDR_REQUIRE(a->variant < 20, GSDR_E_UNSUPPORTED,
         "%s: fft_size %u runs on a four-step plan; the folding forward transform needs a one-launch LDS plan", who,
         a->N);
@@ -93,33 +85,25 @@ int check_quick_handle(const gsdr_acq* a, const char* who)
 int check_quick_run(const gsdr_acq* a, const char* who)
 {
     GSDR_REQUIRE(a->qs.p > 0, GSDR_E_STATE, "%s: gsdr_acq_set_quicksync first", who);
-    GSDR_REQUIRE(a->qs.ncodes > 0, GSDR_E_STATE, "%s: gsdr_acq_set_quicksync_codes first", who);
+    GSDR_REQUIRE(a->slots == gsdr_acq::Slots::QuickSync, GSDR_E_STATE, "%s: gsdr_acq_set_quicksync_codes first", who);
     GSDR_REQUIRE(a->wipe_mode == GSDR_WIPE_EXACT, GSDR_E_UNSUPPORTED,
         "%s: QuickSync runs with the exact carrier only (gsdr_acq_set_wipeoff mode %d)", who, a->wipe_mode);
     return GSDR_OK;
 }
 
-// While alive the handle's launches are a QuickSync run's: the folding forward pass
-// (launch_forward, launch_forward_pk) and the CFAR sequence (params_of), whose reduce and
-// selected-row passes give each slot's maximum, row and first index and launch no
-// second-peak pass.
-struct QuickRun
-{
-    gsdr_acq* a;
-    explicit QuickRun(gsdr_acq* a_) : a(a_) { a->qs.running = true; }
-    ~QuickRun() { a->qs.running = false; }
-};
-
 // nitems grids over the active slots at iq (device, items of L at stride L), the input
-// powers, the candidate powers and the records into qs.d_out, on the handle's stream.
+// powers, the candidate powers and the records into qs.d_out, on the handle's stream.  The
+// view carries the run's mode: the rows over an item, the folding forward pass over p^2
+// segments (launch_forward, launch_forward_pk) and no second-peak pass (params_of).
 int enqueue_quick(gsdr_acq* a, const void* iq, uint32_t nitems, uint64_t stamp0)
 {
-    QuickRun mark(a);
     gsdr_acq::Quick& q = a->qs;
     hipStream_t s = a->stream;
     const uint64_t L = (uint64_t)q.p * q.spc;
     AcqView v = view_of(a);
     v.wipe = q.d_wipe;
+    v.fold_segments = q.p * q.p;
+    v.first_peak_only = true;
     const int rc = dispatch(a, v, AcqOp{AcqOp::Run, iq, nitems, L, stamp0, a->d_res, s});
     if (rc != GSDR_OK) return rc;
     StageTimer t(a, s);
@@ -128,7 +112,7 @@ int enqueue_quick(gsdr_acq* a, const void* iq, uint32_t nitems, uint64_t stamp0)
     with_item_type(a->conf.item_type, [&](auto it) {
         hipLaunchKernelGGL((acq_pair_power_kernel<decltype(it)::value>), dim3(nitems), dim3(kPairPowerLanes), 0, s, iq, L,
             (uint32_t)L, q.d_power);
-        hipLaunchKernelGGL((acq_quick_candidate_kernel<decltype(it)::value>), dim3(n, q.cand_loop ? 1u : q.p),
+        hipLaunchKernelGGL((acq_quick_candidate_kernel<decltype(it)::value>), dim3(n, q.p),
             dim3(kQuickCandLanes), 0, s, iq, L, (const float2*)q.d_wipe, (const float2*)a->d_tw,
             (const float2*)q.d_codes, (const gsdr_acq_result*)a->d_res, q.d_cand, v.nprn, v.D, q.p, q.spc, a->N, v.xm);
     });
@@ -137,14 +121,6 @@ int enqueue_quick(gsdr_acq* a, const void* iq, uint32_t nitems, uint64_t stamp0)
         (const float*)q.d_power, (const float*)q.d_cand, q.d_out, v.nprn, n, q.p, a->N);
     GSDR_HIP(hipGetLastError());
     t.end(2);
-    return GSDR_OK;
-}
-
-int read_quick_results(gsdr_acq* a, gsdr_acq_quicksync_result* out, uint32_t nitems)
-{
-    GSDR_HIP(hipMemcpyAsync(out, a->qs.d_out, (size_t)nitems * a->nprn * sizeof(gsdr_acq_quicksync_result),
-        hipMemcpyDeviceToHost, a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
     return GSDR_OK;
 }
 
@@ -201,8 +177,6 @@ int gsdr_acq_set_quicksync(gsdr_acq* a, uint32_t folding_factor, uint32_t sample
         }
     q.p = p;
     q.spc = spc;
-    const char* loop = std::getenv("GSDR_ACQ_QS_CAND_LOOP");
-    q.cand_loop = loop && loop[0] == '1' && loop[1] == '\0';
     rc = quicksync_rebuild_wipeoffs(a);
     if (rc == GSDR_OK && hipStreamSynchronize(a->stream) != hipSuccess) rc = GSDR_E_DEVICE;
     if (rc != GSDR_OK) quicksync_free(a);
@@ -229,9 +203,7 @@ int gsdr_acq_set_quicksync_codes(gsdr_acq* a, const float* codes, const uint32_t
     const int rc = code_fft(a, 0, nprn);
     if (rc != GSDR_OK) return rc;
     GSDR_HIP(hipStreamSynchronize(a->stream));  // codes and prn are read until here
-    a->nprn = nprn;
-    a->pairs.npairs = 0;
-    q.ncodes = nprn;
+    set_slots(a, gsdr_acq::Slots::QuickSync, nprn);
     return GSDR_OK;
 }
 
@@ -239,10 +211,10 @@ int gsdr_acq_run_quicksync(gsdr_acq* a, const void* iq_host, uint32_t nitems, ui
     gsdr_acq_quicksync_result* out)
 {
     GSDR_REQUIRE(a && iq_host && out, GSDR_E_ARG, "gsdr_acq_run_quicksync: null argument");
-    GSDR_REQUIRE(nitems > 0 && nitems <= a->conf.max_blocks, GSDR_E_ARG,
-        "gsdr_acq_run_quicksync: nitems %u outside [1,%u]", nitems, a->conf.max_blocks);
+    int rc = check_block_count(a, "gsdr_acq_run_quicksync", nitems, "nitems");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
-    int rc = check_quick_run(a, "gsdr_acq_run_quicksync");
+    rc = check_quick_run(a, "gsdr_acq_run_quicksync");
     if (rc != GSDR_OK) return rc;
     gsdr::DeviceGuard g(a->device);
     const size_t L = (size_t)a->qs.p * a->qs.spc;
@@ -250,35 +222,26 @@ int gsdr_acq_run_quicksync(gsdr_acq* a, const void* iq_host, uint32_t nitems, ui
         a->stream));
     rc = enqueue_quick(a, a->qs.d_iq, nitems, stamp0);
     if (rc != GSDR_OK) return rc;
-    return read_quick_results(a, out, nitems);
+    return read_back(a, out, a->qs.d_out, (size_t)nitems * a->nprn * sizeof(gsdr_acq_quicksync_result));
 }
 
 int gsdr_acq_run_quicksync_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nitems,
     uint64_t stamp0, gsdr_acq_quicksync_result* out)
 {
     GSDR_REQUIRE(a && ring && out, GSDR_E_ARG, "gsdr_acq_run_quicksync_stream: null argument");
-    GSDR_REQUIRE(nitems > 0 && nitems <= a->conf.max_blocks, GSDR_E_ARG,
-        "gsdr_acq_run_quicksync_stream: nitems %u outside [1,%u]", nitems, a->conf.max_blocks);
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == a->conf.item_type, GSDR_E_ARG,
-        "gsdr_acq_run_quicksync_stream: ring item type %d != acquisition item type %d", gsdr::stream_item_type(ring),
-        a->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == a->device, GSDR_E_ARG,
-        "gsdr_acq_run_quicksync_stream: ring on device %d, acquisition handle on device %d", gsdr::stream_device(ring),
-        a->device);
+    int rc = check_block_count(a, "gsdr_acq_run_quicksync_stream", nitems, "nitems");
+    if (rc == GSDR_OK)
+        rc = gsdr::check_ring_consumer("gsdr_acq_run_quicksync_stream", ring, a->conf.item_type, a->device,
+            "acquisition");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
-    int rc = check_quick_run(a, "gsdr_acq_run_quicksync_stream");
+    rc = check_quick_run(a, "gsdr_acq_run_quicksync_stream");
     if (rc != GSDR_OK) return rc;
     gsdr::DeviceGuard g(a->device);
-    {
-        gsdr::StreamReader rd(ring);  // ring lock from view to reader-event record
-        const void* iq = nullptr;
-        rc = rd.view(first_sample, (uint64_t)nitems * a->qs.p * a->qs.spc, &iq);
-        if (rc == GSDR_OK) rc = rd.acquire(a->stream);
-        if (rc == GSDR_OK) rc = enqueue_quick(a, iq, nitems, stamp0);
-        if (rc == GSDR_OK) rc = rd.release(a->stream);
-    }
+    rc = with_ring_items(a, ring, first_sample, (uint64_t)nitems * a->qs.p * a->qs.spc,
+        [&](const void* iq) { return enqueue_quick(a, iq, nitems, stamp0); });
     if (rc != GSDR_OK) return rc;
-    return read_quick_results(a, out, nitems);
+    return read_back(a, out, a->qs.d_out, (size_t)nitems * a->nprn * sizeof(gsdr_acq_quicksync_result));
 }
 
 int gsdr_acq_dump_quicksync(gsdr_acq* a, const void* iq_host, float* rows_out, float* cand_out)
@@ -295,17 +258,12 @@ int gsdr_acq_dump_quicksync(gsdr_acq* a, const void* iq_host, float* rows_out, f
     // stats[p D + d]
     rc = enqueue_quick(a, a->qs.d_iq, 1, 0);
     if (rc != GSDR_OK) return rc;
-    const uint32_t P = a->nprn, D = a->D;
-    std::vector<RowStat> st((size_t)P * D);
-    GSDR_HIP(hipMemcpyAsync(st.data(), a->d_stats, st.size() * sizeof(RowStat), hipMemcpyDeviceToHost, a->stream));
     if (cand_out)
-        GSDR_HIP(hipMemcpyAsync(cand_out, a->qs.d_cand, (size_t)P * a->qs.p * sizeof(float), hipMemcpyDeviceToHost,
+        GSDR_HIP(hipMemcpyAsync(cand_out, a->qs.d_cand, (size_t)a->nprn * a->qs.p * sizeof(float), hipMemcpyDeviceToHost,
             a->stream));
-    GSDR_HIP(hipStreamSynchronize(a->stream));
     const float norm = (float)a->N * (float)a->N;
-    if (rows_out)
-        for (uint32_t d = 0; d < D; ++d)
-            for (uint32_t p = 0; p < P; ++p) rows_out[(size_t)d * P + p] = st[(size_t)p * D + d].max / (norm * norm);
+    if (rows_out) return row_maxima_to_host(a, a->nprn, a->D, norm * norm, rows_out);
+    GSDR_HIP(hipStreamSynchronize(a->stream));
     return GSDR_OK;
 }
 

@@ -110,8 +110,7 @@ __global__ void __launch_bounds__(MP::NT) acq_forward_fold_pk_kernel(const void*
 // |acc_i|^2.  The last read is sample (Nf - 1) + (p - 1) Nf + spc - 1 = 2 spc - 2 < L for p >= 2.
 // w_d is the row's own wipe-off: the stored row c = d mod q times the shift's phasor
 // W_Nf^{a p (n mod Nf)}, a = d / q, from the handle's twiddle table (XMap; p = 0: the row itself).
-// blockIdx.x = b nprn + slot; the workgroups of blockIdx.y share the candidates i = blockIdx.y,
-// blockIdx.y + gridDim.y, ... (gridDim.y = p: one each; 1: one workgroup loops over all).
+// blockIdx.x = b nprn + slot, blockIdx.y = i (gridDim.y = p): one workgroup per candidate.
 constexpr int kQuickCandLanes = 1024;
 
 template <int IT>
@@ -122,7 +121,7 @@ __global__ void __launch_bounds__(kQuickCandLanes) acq_quick_candidate_kernel(co
 {
     constexpr int NW = kQuickCandLanes / 64;
     __shared__ float2 s_acc[NW];
-    const uint32_t bp = blockIdx.x;
+    const uint32_t bp = blockIdx.x, i = blockIdx.y;
     const uint32_t b = bp / nprn, slot = bp - b * nprn;
     // the device record's winner, kept inside the grid whatever it holds
     const uint32_t d = min(res[bp].doppler_index, D - 1);
@@ -131,40 +130,36 @@ __global__ void __launch_bounds__(kQuickCandLanes) acq_quick_candidate_kernel(co
     const size_t base = (size_t)b * item_stride;
     const float2* w = wipe + (size_t)c * p * spc;
     const float2* code = codes + (size_t)slot * spc;
-    for (uint32_t i = blockIdx.y; i < p; i += gridDim.y)
-        {
-            const uint32_t delay = t + i * nf;
-            float2 acc = make_float2(0.f, 0.f);
+    const uint32_t delay = t + i * nf;
+    float2 acc = make_float2(0.f, 0.f);
 #pragma unroll 2
-            for (uint32_t j = threadIdx.x; j < spc; j += kQuickCandLanes)
-                {
-                    const uint32_t n = delay + j;
-                    float2 wv = w[n];
-                    if (shift) wv = gsdr::fft::cmul(wv, tw[(shift * (n % nf)) % nf]);
-                    const float2 y = gsdr::fft::cmul(gsdr::fft::cmul(load_item<IT>(iq, base + n), wv), code[j]);
-                    acc.x += y.x;
-                    acc.y += y.y;
-                }
+    for (uint32_t j = threadIdx.x; j < spc; j += kQuickCandLanes)
+        {
+            const uint32_t n = delay + j;
+            float2 wv = w[n];
+            if (shift) wv = gsdr::fft::cmul(wv, tw[(shift * (n % nf)) % nf]);
+            const float2 y = gsdr::fft::cmul(gsdr::fft::cmul(load_item<IT>(iq, base + n), wv), code[j]);
+            acc.x += y.x;
+            acc.y += y.y;
+        }
 #pragma unroll
-            for (int off = 32; off > 0; off >>= 1)
-                {
-                    acc.x += __shfl_xor(acc.x, off);
-                    acc.y += __shfl_xor(acc.y, off);
-                }
-            if ((threadIdx.x & 63) == 0) s_acc[threadIdx.x >> 6] = acc;
-            __syncthreads();
-            if (threadIdx.x == 0)
-                {
-                    float2 tot = make_float2(0.f, 0.f);
+    for (int off = 32; off > 0; off >>= 1)
+        {
+            acc.x += __shfl_xor(acc.x, off);
+            acc.y += __shfl_xor(acc.y, off);
+        }
+    if ((threadIdx.x & 63) == 0) s_acc[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        {
+            float2 tot = make_float2(0.f, 0.f);
 #pragma unroll
-                    for (int wv = 0; wv < NW; ++wv)
-                        {
-                            tot.x += s_acc[wv].x;
-                            tot.y += s_acc[wv].y;
-                        }
-                    cand[(size_t)bp * p + i] = tot.x * tot.x + tot.y * tot.y;
+            for (int wv = 0; wv < NW; ++wv)
+                {
+                    tot.x += s_acc[wv].x;
+                    tot.y += s_acc[wv].y;
                 }
-            __syncthreads();  // s_acc is the next candidate's too
+            cand[(size_t)bp * p + i] = tot.x * tot.x + tot.y * tot.y;
         }
 }
 

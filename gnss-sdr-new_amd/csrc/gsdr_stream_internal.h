@@ -13,6 +13,9 @@ namespace gsdr
 {
 int stream_item_type(const gsdr_stream* s);
 int stream_device(const gsdr_stream* s);
+// GSDR_E_ARG, with the message, unless the ring holds the consumer's item type on its
+// device; `who` names the call and `noun` the consumer ("acquisition", "tracking")
+int check_ring_consumer(const char* who, const gsdr_stream* ring, int item_type, int device, const char* noun);
 
 // A consumer launch reads the ring under one hold of the ring's lock, from
 // choosing its window to recording its reader event, so a push from another

@@ -83,6 +83,15 @@ uint64_t stream_capacity(const gsdr_stream* s) { return s->cap; }
 uint64_t stream_window(const gsdr_stream* s) { return s->window; }
 void stream_set_device_produced(gsdr_stream* s) { s->device_produced = true; }
 
+int check_ring_consumer(const char* who, const gsdr_stream* ring, int item_type, int device, const char* noun)
+{
+    GSDR_REQUIRE(ring->item_type == item_type, GSDR_E_ARG, "%s: ring item type %d != %s item type %d", who,
+        ring->item_type, noun, item_type);
+    GSDR_REQUIRE(ring->device == device, GSDR_E_ARG, "%s: ring on device %d, %s handle on device %d", who, ring->device,
+        noun, device);
+    return GSDR_OK;
+}
+
 namespace
 {
 uint64_t oldest_of(const gsdr_stream* s) { return s->head > s->cap ? std::max(s->base, s->head - s->cap) : s->base; }

@@ -2858,17 +2858,14 @@ int gsdr_trk_run_stream(gsdr_trk* k, gsdr_stream* ring, uint32_t max_epochs, gsd
     uint32_t* n_out_dev, void* stream)
 {
     GSDR_REQUIRE(k && ring && out_dev && n_out_dev, GSDR_E_ARG, "gsdr_trk_run_stream: null argument");
-    GSDR_REQUIRE(gsdr::stream_item_type(ring) == k->conf.item_type, GSDR_E_ARG,
-        "gsdr_trk_run_stream: ring item type %d != tracking item type %d", gsdr::stream_item_type(ring),
-        k->conf.item_type);
-    GSDR_REQUIRE(gsdr::stream_device(ring) == k->device, GSDR_E_ARG,
-        "gsdr_trk_run_stream: ring on device %d, tracking handle on device %d", gsdr::stream_device(ring), k->device);
+    int rc = gsdr::check_ring_consumer("gsdr_trk_run_stream", ring, k->conf.item_type, k->device, "tracking");
+    if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(k->mu);
     gsdr::DeviceGuard g(k->device);
     hipStream_t s = stream ? (hipStream_t)stream : k->stream;
     gsdr::StreamReader rd(ring);  // ring lock from window choice to reader-event record
     uint64_t first = 0, n = 0;
-    int rc = rd.span(&first, &n);
+    rc = rd.span(&first, &n);
     if (rc != GSDR_OK) return rc;
     const void* iq = nullptr;
     rc = rd.view(first, n, &iq);

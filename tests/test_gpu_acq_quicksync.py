@@ -294,6 +294,64 @@ def test_plain_run_is_unchanged(name, pfa):
     acq.close()
 
 
+def test_modes_share_a_handle():
+    """One handle moved QuickSync -> pairs -> plain (peak ratio) -> QuickSync: each mode's records
+    are the bytes of a handle that ran only that mode, the two QuickSync runs are the same bytes,
+    and a mode whose codes are not the ones in the slots is refused with GSDR_E_STATE.  The smallest
+    shape on the packed forward (variant 62, N = 2000)."""
+    c = qc.quick_case("q4000x2")
+    assert len(c.prns) == 4
+    prns = np.array(c.prns, np.uint32)
+    plain = np.ascontiguousarray(c.codes[:, :c.nf])
+    first, second, pair_prns = plain[0::2], plain[1::2], prns[0::2]
+    flat = c.items()[0]
+    x = flat[:qc.NITEMS * c.nf]
+
+    def handle():
+        return _handle(c, max_prns=4, max_blocks=qc.NITEMS)
+
+    def refused(call):
+        with pytest.raises(gsdr.GsdrError) as e:
+            call()
+        assert e.value.code == gsdr.GSDR_E_STATE, e.value
+        return True
+
+    only = handle()
+    assert only.plan["variant"] < 20 and only.fft_size == 2000
+    only.set_local_codes(plain, prns)
+    want_plain = only.run(x, nblocks=qc.NITEMS, stamp0=STAMP0)
+    only.close()
+    only = handle()
+    only.set_code_pairs(gsdr.PAIR_AS_IS, first, second, pair_prns)
+    want_pairs = only.run_pairs(x, nblocks=qc.NITEMS, stamp0=STAMP0)
+    only.close()
+    only = _quick(c, max_prns=4)
+    want_quick = only.run_quicksync(flat, nitems=qc.NITEMS, stamp0=STAMP0)
+    only.close()
+    assert want_plain.shape == (qc.NITEMS, 4) and want_pairs.shape == (qc.NITEMS, 2)
+    assert want_quick.shape == (qc.NITEMS, 4)
+
+    acq = handle()
+    acq.set_quicksync(c.p, c.spc)
+    acq.set_quicksync_codes(c.codes, prns)
+    quick1 = acq.run_quicksync(flat, nitems=qc.NITEMS, stamp0=STAMP0)
+    assert refused(lambda: acq.run_pairs(x, nblocks=qc.NITEMS))
+    acq.set_code_pairs(gsdr.PAIR_AS_IS, first, second, pair_prns)
+    pairs = acq.run_pairs(x, nblocks=qc.NITEMS, stamp0=STAMP0)
+    assert refused(lambda: acq.run_quicksync(flat, nitems=qc.NITEMS))
+    acq.set_local_codes(plain, prns)
+    got_plain = acq.run(x, nblocks=qc.NITEMS, stamp0=STAMP0)
+    assert refused(lambda: acq.run_pairs(x, nblocks=qc.NITEMS))
+    assert refused(lambda: acq.run_quicksync(flat, nitems=qc.NITEMS))
+    acq.set_quicksync_codes(c.codes, prns)
+    quick2 = acq.run_quicksync(flat, nitems=qc.NITEMS, stamp0=STAMP0)
+    acq.close()
+    assert quick1.tobytes() == want_quick.tobytes()
+    assert pairs.tobytes() == want_pairs.tobytes()
+    assert got_plain.tobytes() == want_plain.tobytes()
+    assert quick2.tobytes() == quick1.tobytes()
+
+
 def test_doppler_grid_moved_after_configuring():
     """gsdr_acq_set_doppler rebuilds the wipe-off rows over the item too."""
     c = qc.quick_case("q4000x4")

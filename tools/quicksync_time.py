@@ -1,7 +1,6 @@
 """QuickSync cost on the GPU ("QuickSync"): per-stage device-event times and wall
 time per call of gsdr_acq_run_quicksync at 25 / 8 / 4 Msps against the plain search at the same rate
-(8 PRNs, 41 rows), with the two shapes of the candidate check (GSDR_ACQ_QS_CAND_LOOP) alternated,
-twice.  One JSON line per configuration.
+(8 PRNs, 41 rows), two rounds.  One JSON line per configuration.
 
     python tools/quicksync_time.py [calls per figure, default 50] [items per call, default 4] > out.jsonl
 """
@@ -40,8 +39,7 @@ def wall(call, reps):
     return (time.perf_counter() - t) / reps * 1e3
 
 
-def quick(fs, spc, p, dmax, items, loop, reps):
-    os.environ["GSDR_ACQ_QS_CAND_LOOP"] = "1" if loop else "0"
+def quick(fs, spc, p, dmax, items, reps):
     nf, L = spc // p, p * spc
     D = 2 * dmax // 250 + 1
     acq = gsdr.Acquisition(fs, nf, dmax, 250, max_prns=len(PRNS), max_blocks=items, samples_per_code=float(spc),
@@ -52,7 +50,7 @@ def quick(fs, spc, p, dmax, items, loop, reps):
     call = lambda: acq.run_quicksync(x, nitems=items)
     st, n = stages(acq, call, reps)
     w = wall(call, reps)
-    rec = dict(kind="quicksync", fs=fs, spc=spc, p=p, nf=nf, D=D, items=items, prns=len(PRNS), cand_loop=loop,
+    rec = dict(kind="quicksync", fs=fs, spc=spc, p=p, nf=nf, D=D, items=items, prns=len(PRNS),
                plan=acq.plan["variant"], reuse=acq.spectrum_reuse, stage_ms=st, launches=n, wall_ms=w,
                ms_of_signal=items * L / fs * 1e3)
     acq.close()
@@ -77,11 +75,10 @@ def plain(fs, spc, dmax, blocks, reps):
 if __name__ == "__main__":
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     items = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-    for rnd in range(2):  # alternate, twice
-        for loop in (False, True):
-            quick(25000000, 25000, 4, 5000, items, loop, reps)
-            quick(8000000, 8000, 2, 5000, items, loop, reps)
-            quick(4000000, 4000, 4, 5000, items, loop, reps)
+    for rnd in range(2):
+        quick(25000000, 25000, 4, 5000, items, reps)
+        quick(8000000, 8000, 2, 5000, items, reps)
+        quick(4000000, 4000, 4, 5000, items, reps)
         plain(25000000, 25000, 5000, items, reps)
         plain(8000000, 8000, 5000, items, reps)
         plain(4000000, 4000, 5000, items, reps)
