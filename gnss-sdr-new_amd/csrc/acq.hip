@@ -19,6 +19,9 @@
 //   K_quick   QuickSync (pcps_quicksync_acquisition_cc): the folded code, the folding forward
 //                     transform in place of K_forward, the item's input power and the check of
 //                     the p delays the folded winner stands for (acq_quicksync.hip)
+//   K_tong    Tong (pcps_tong_acquisition_cc): the grid accumulated over a sequence of items, each
+//                     scaled by its own input power, walked by one workgroup per row, and the
+//                     counter over the items' maxima (acq_tong.hip)
 //   K_pair    paired codes (pcps_cccwsr_acquisition_cc, galileo_pcps_8ms_acquisition_cc): the
 //                     two replicas of a pair, the block's input power and the merge of a
 //                     pair's two slot records, around the kernels above (acq_pair.hip)
@@ -102,7 +105,6 @@ hipError_t upload_twiddles(float2* d_tw, uint32_t n)
 
 // Pick a compile-time plan when one matches N, else the smallest workgroup that
 // admits a runtime plan, else a four-step plan (acq_plans.h).
-constexpr size_t kLdsBytes = 160 * 1024;
 
 void set_four(gsdr_acq* a, int id, int nt, int r1, const Plan& sub)
 {
@@ -320,6 +322,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
     fine_free(a);
     pairs_free(a);
     quicksync_free(a);
+    tong_free(a);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }

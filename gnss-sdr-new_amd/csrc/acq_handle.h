@@ -150,6 +150,19 @@ struct gsdr_acq
         float* d_cand{nullptr};   // max_blocks x max_prns x p candidate powers
         gsdr_acq_quicksync_result* d_out{nullptr};  // max_blocks x max_prns records
     } qs;
+    // Tong acquisition (gsdr_acq_set_tong / gsdr_acq_run_tong, acq_tong.hip): the buffers are
+    // built by gsdr_acq_set_tong
+    struct Tong
+    {
+        uint32_t init{0}, max{0}, max_dwells{0};  // tong_init_val, tong_max_val (> 0: configured), tong_max_dwells
+        bool row_lds{false};  // the grid kernel keeps its running row in LDS beside the transform's buffer
+        float* d_grid{nullptr};   // max_prns x D x N accumulated rows
+        gsdr_acq_impl::TongSlot* d_slots{nullptr};  // max_prns sequence states
+        float* d_power{nullptr};  // max_blocks input powers
+        float* d_scale{nullptr};  // max_blocks scales 1 / (fn fn P_k)
+        gsdr_acq_impl::RowStat* d_stats{nullptr};   // max_blocks x max_prns x D row maxima of the accumulated rows
+        gsdr_acq_tong_result* d_out{nullptr};       // max_blocks x max_prns records
+    } tong;
     std::mutex mu;
 };
 
@@ -178,6 +191,13 @@ struct AcqView
     // the CFAR launch sequence whatever conf.pfa says: its reduce and selected-row passes
     // give each slot's maximum, row and first index, and no second-peak pass follows
     bool first_peak_only{false};
+    // a Tong run (AcqOp::Tong, acq_tong.hip): the accumulated grid, the items' scales, the
+    // slots' sequence states, where the row maxima go and where the running row is kept
+    float* tong_grid{nullptr};
+    const float* tong_scale{nullptr};
+    const TongSlot* tong_slots{nullptr};
+    RowStat* tong_stats{nullptr};
+    bool tong_row_lds{false};
 };
 
 // The operation of a per-plan dispatch, with the arguments each kind reads.
@@ -190,7 +210,8 @@ struct AcqOp
         DumpSpectra,  // (the block at d_iq)
         DumpGrid,     // prn_slot
         SetAttrs,
-        Dwell         // dwell, stamp0, res, s
+        Dwell,        // dwell, stamp0, res, s
+        Tong          // iq, nblocks, stride, s (the view's tong_* fields)
     } kind;
     const void* iq{nullptr};
     uint32_t nblocks{0};
@@ -199,6 +220,17 @@ struct AcqOp
     hipStream_t s{nullptr};
     uint32_t first_slot{0}, nslots{0}, prn_slot{0}, dwell{0};
 };
+
+// The LDS a workgroup of the engine may ask for (choose_variant, acq.hip).
+constexpr size_t kLdsBytes = 160 * 1024;
+
+// Dynamic LDS of acq_tong_grid_kernel on the handle's plan: with the running row of N floats
+// behind the transform's buffer and the statistics scratch where that fits the limit.
+inline bool tong_row_fits_lds(const gsdr_acq* a) { return a->lds_bytes + (size_t)a->N * sizeof(float) <= kLdsBytes; }
+inline size_t tong_lds_bytes(const gsdr_acq* a)
+{
+    return a->lds_bytes + (tong_row_fits_lds(a) ? (size_t)a->N * sizeof(float) : 0);
+}
 
 // Default packed correlate variant for an FFT size (0: none, the generic kernels).
 inline int default_pk_variant(uint32_t N)
@@ -330,6 +362,8 @@ void pairs_free(gsdr_acq* a);
 // configured), free the QuickSync buffers
 int quicksync_rebuild_wipeoffs(gsdr_acq* a);
 void quicksync_free(gsdr_acq* a);
+// acq_tong.hip: free the Tong buffers
+void tong_free(gsdr_acq* a);
 // acq.hip: the per-plan dispatch of an op, and the code spectra (with their lane-order
 // copies) of slots [first_slot, first_slot + nslots) from their staged codes
 int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op);

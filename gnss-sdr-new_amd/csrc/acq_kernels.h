@@ -47,6 +47,17 @@ struct XMap
     }
 };
 
+// A code slot's Tong sequence (pcps_tong_acquisition_cc: d_dwell_count, d_tong_count, d_state),
+// kept on the device between calls.  dwell_count == 0 marks a slot that has seen no item since
+// its reset: its rows start from zero instead of being loaded.
+struct TongSlot
+{
+    uint32_t dwell_count;
+    uint32_t tong_count;
+    uint32_t state;  // GSDR_TONG_RUNNING, _POSITIVE, _NEGATIVE
+    uint32_t pad;
+};
+
 struct AcqParams
 {
     XMap xm;             // forward-spectrum layout (see XMap)

@@ -5,6 +5,7 @@
 #include "acq_handle.h"
 #include "acq_plans.h"
 #include "acq_quicksync_kernels.h"
+#include "acq_tong_kernels.h"
 
 namespace
 {
@@ -259,6 +260,57 @@ int launch_dwell(gsdr_acq* a, const AcqView& v, const AcqOp& op)
     return launch_grid_second_peak(a, ap, op.res, s);
 }
 
+// Whether a plan type's Tong grid kernel is built with the running row in LDS, in HBM or both:
+// a compile-time plan knows its size.
+template <class PT>
+constexpr bool tong_may_row_lds()
+{
+    return PT::N == 0 || (size_t)PT::N * (sizeof(float2) + sizeof(float)) + 16 * sizeof(RowStat) <= kLdsBytes;
+}
+template <class PT>
+constexpr bool tong_may_row_hbm()
+{
+    return PT::N == 0 || !tong_may_row_lds<PT>();
+}
+
+template <class PT>
+int set_tong_attrs(const gsdr_acq* a)
+{
+    int rc = GSDR_OK;
+    if constexpr (tong_may_row_lds<PT>())
+        if (tong_row_fits_lds(a)) rc |= set_max_lds((const void*)acq_tong_grid_kernel<PT, true>, tong_lds_bytes(a));
+    if constexpr (tong_may_row_hbm<PT>())
+        if (!tong_row_fits_lds(a)) rc |= set_max_lds((const void*)acq_tong_grid_kernel<PT, false>, tong_lds_bytes(a));
+    return rc == GSDR_OK ? GSDR_OK : GSDR_E_DEVICE;
+}
+
+// gsdr_acq_run_tong: forward spectra of the nblocks items at op.iq and the grid kernel over
+// them on the view's Tong buffers.
+template <class PT>
+int launch_tong(gsdr_acq* a, const AcqView& v, const AcqOp& op)
+{
+    hipStream_t s = op.s;
+    StageTimer t(a, s);
+    t.begin();
+    launch_forward<PT>(a, v, op.iq, op.nblocks, op.stride, s);
+    GSDR_HIP(hipGetLastError());
+    t.end(0);
+    t.begin();
+    if constexpr (tong_may_row_lds<PT>())
+        if (v.tong_row_lds)
+            hipLaunchKernelGGL((acq_tong_grid_kernel<PT, true>), dim3(v.D * v.nprn), dim3(PT::NT), tong_lds_bytes(a), s,
+                a->d_X, v.code_fft, v.tong_stats, a->d_tw, plan_of<PT>(a), v.tong_grid, v.tong_scale, v.tong_slots, v.D,
+                v.nprn, op.nblocks, v.xm);
+    if constexpr (tong_may_row_hbm<PT>())
+        if (!v.tong_row_lds)
+            hipLaunchKernelGGL((acq_tong_grid_kernel<PT, false>), dim3(v.D * v.nprn), dim3(PT::NT), tong_lds_bytes(a), s,
+                a->d_X, v.code_fft, v.tong_stats, a->d_tw, plan_of<PT>(a), v.tong_grid, v.tong_scale, v.tong_slots, v.D,
+                v.nprn, op.nblocks, v.xm);
+    GSDR_HIP(hipGetLastError());
+    t.end(1);
+    return GSDR_OK;
+}
+
 // Code spectra of slots [first_slot, first_slot + nslots) from their staged codes.
 template <class PT>
 int launch_code_fft(gsdr_acq* a, const AcqOp& op)
@@ -295,7 +347,19 @@ int run_op(gsdr_acq* a, const AcqView& v, const AcqOp& op)
         case AcqOp::DumpSpectra: return launch_dump<PT>(a, v, false, 0);
         case AcqOp::DumpGrid: return launch_dump<PT>(a, v, true, op.prn_slot);
         case AcqOp::Dwell: return launch_dwell<PT>(a, v, op);
-        case AcqOp::SetAttrs: return set_lds_attrs<PT>(a->lds_bytes);
+        case AcqOp::SetAttrs:
+            {
+                const int rc = set_lds_attrs<PT>(a->lds_bytes);
+                if constexpr (!std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
+                    if (rc == GSDR_OK) return set_tong_attrs<PT>(a);
+                return rc;
+            }
+        case AcqOp::Tong:
+            // LDS plans only (gsdr_acq_set_tong refuses the four-step sizes)
+            if constexpr (!std::is_same<typename PT::PlanT, gsdr::fft::Plan4>::value)
+                return launch_tong<PT>(a, v, op);
+            else
+                break;
         }
     return GSDR_E_STATE;
 }

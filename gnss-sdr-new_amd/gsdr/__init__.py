@@ -57,6 +57,8 @@ EXPORTED = [
     "gsdr_acq_set_code_pairs", "gsdr_acq_run_pairs", "gsdr_acq_run_pairs_stream", "gsdr_acq_dump_pair_rows",
     "gsdr_acq_set_quicksync", "gsdr_acq_set_quicksync_codes", "gsdr_acq_run_quicksync",
     "gsdr_acq_run_quicksync_stream", "gsdr_acq_dump_quicksync",
+    "gsdr_acq_set_tong", "gsdr_acq_tong_reset", "gsdr_acq_run_tong", "gsdr_acq_run_tong_stream",
+    "gsdr_acq_dump_tong_grid",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -285,6 +287,33 @@ assert all(ACQ_QUICKSYNC_RESULT_DTYPE.fields[f][1] == getattr(AcqQuickSyncResult
            for f, _ in AcqQuickSyncResult._fields_)
 
 
+class AcqTongResult(ctypes.Structure):
+    """gsdr_acq_tong_result: one (item, PRN) outcome of gsdr_acq_run_tong."""
+    _fields_ = [
+        ("prn", ctypes.c_uint32),
+        ("doppler_index", ctypes.c_uint32),
+        ("indext", ctypes.c_uint32),
+        ("doppler_hz", ctypes.c_int32),
+        ("acq_delay_samples", ctypes.c_double),
+        ("samplestamp", ctypes.c_uint64),
+        ("mag", ctypes.c_float),
+        ("input_power", ctypes.c_float),
+        ("dwell_count", ctypes.c_uint32),
+        ("tong_count", ctypes.c_uint32),
+        ("state", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+ACQ_TONG_RESULT_DTYPE = np.dtype([
+    ("prn", np.uint32), ("doppler_index", np.uint32), ("indext", np.uint32), ("doppler_hz", np.int32),
+    ("acq_delay_samples", np.float64), ("samplestamp", np.uint64), ("mag", np.float32), ("input_power", np.float32),
+    ("dwell_count", np.uint32), ("tong_count", np.uint32), ("state", np.uint32), ("pad", np.uint32)])
+assert ACQ_TONG_RESULT_DTYPE.itemsize == ctypes.sizeof(AcqTongResult)
+assert all(ACQ_TONG_RESULT_DTYPE.fields[f][1] == getattr(AcqTongResult, f).offset for f, _ in AcqTongResult._fields_)
+TONG_RUNNING, TONG_POSITIVE, TONG_NEGATIVE, TONG_PAST_END = 0, 1, 2, 3
+
+
 class CorrJob(ctypes.Structure):
     _fields_ = [
         ("channel", ctypes.c_int32),
@@ -358,6 +387,12 @@ def load():
         L.gsdr_acq_run_quicksync.argtypes = [P, P, U32, U64, P]
         L.gsdr_acq_run_quicksync_stream.argtypes = [P, P, U64, U32, U64, P]
         L.gsdr_acq_dump_quicksync.argtypes = [P, P, P, P]
+    if hasattr(L, "gsdr_acq_set_tong"):  # (as above)
+        L.gsdr_acq_set_tong.argtypes = [P, U32, U32, U32]
+        L.gsdr_acq_tong_reset.argtypes = [P, P, U32]
+        L.gsdr_acq_run_tong.argtypes = [P, P, U32, U64, P]
+        L.gsdr_acq_run_tong_stream.argtypes = [P, P, U64, U32, U64, P]
+        L.gsdr_acq_dump_tong_grid.argtypes = [P, U32, P]
     L.gsdr_corr_create.argtypes = [I, I, I, I, P]
     L.gsdr_corr_destroy.argtypes = [P]
     L.gsdr_corr_destroy.restype = None
@@ -847,6 +882,82 @@ class Acquisition:
         cand = np.zeros((max(self.nprn, 1), max(getattr(self, "folding_factor", 0), 1)), np.float32)
         _check(load().gsdr_acq_dump_quicksync(self._h, _ptr(iq), _ptr(rows), _ptr(cand)))
         return rows, cand
+
+
+    # ---- Tong (pcps_tong_acquisition_cc)
+    def set_tong(self, tong_init_val, tong_max_val, tong_max_dwells):
+        """gsdr_acq_set_tong: the handle keeps a Tong sequence per code slot from now on (the
+        codes are set_local_codes', the threshold set_threshold's)."""
+        _check(load().gsdr_acq_set_tong(self._h, int(tong_init_val), int(tong_max_val), int(tong_max_dwells)))
+
+    def tong_reset(self, slots=None):
+        """gsdr_acq_tong_reset: set_state(1) of the given code slots (None: all)."""
+        if slots is None:
+            _check(load().gsdr_acq_tong_reset(self._h, None, 0))
+        else:
+            slots = np.ascontiguousarray(slots, np.uint32)
+            _check(load().gsdr_acq_tong_reset(self._h, _ptr(slots), len(slots)))
+
+    def run_tong(self, iq, nitems=1, stamp0=0, first_sample=0):
+        """gsdr_acq_run_tong: nitems consecutive host items of fft_size samples, or, with a
+        Stream for iq, gsdr_acq_run_tong_stream on its items from first_sample -> structured
+        array [nitems, nprn] (ACQ_TONG_RESULT_DTYPE)."""
+        out = np.zeros(nitems * max(self.nprn, 1), ACQ_TONG_RESULT_DTYPE)
+        if isinstance(iq, Stream):
+            _check(load().gsdr_acq_run_tong_stream(self._h, iq._h, int(first_sample), int(nitems), int(stamp0),
+                                                   _ptr(out)))
+            return out.reshape(nitems, -1)
+        iq = self._items(iq)
+        need = nitems * self.fft_size * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        _check(load().gsdr_acq_run_tong(self._h, _ptr(iq), int(nitems), int(stamp0), _ptr(out)))
+        return out.reshape(nitems, -1)
+
+    def dump_tong_grid(self, prn_slot):
+        """gsdr_acq_dump_tong_grid -> the slot's accumulated grid float32 [num_doppler_bins, fft_size]."""
+        g = np.zeros((self.num_doppler_bins, self.fft_size), np.float32)
+        _check(load().gsdr_acq_dump_tong_grid(self._h, int(prn_slot), _ptr(g)))
+        return g
+
+
+def tong_decide(stats, threshold, tong_init_val, tong_max_val, tong_max_dwells):
+    """The counter of pcps_tong_acquisition_cc (:349-372) on one satellite's statistics, one per
+    dwell in order -> a list of (dwell_count, tong_count, state) per statistic, state one of
+    TONG_RUNNING, TONG_POSITIVE, TONG_NEGATIVE and, after the terminal dwell, TONG_PAST_END
+    with the final counts.  The comparison is the block's, in float: stat > threshold *
+    float(dwell_count).  The tong_max_dwells rule comes last and overrides a positive reached
+    on that same dwell."""
+    assert 1 <= int(tong_init_val) < int(tong_max_val) and int(tong_max_dwells) >= 1
+    thr = np.float32(threshold)
+    dwell, count, state = 0, int(tong_init_val), TONG_RUNNING
+    out = []
+    for s in stats:
+        if state != TONG_RUNNING:
+            out.append((dwell, count, TONG_PAST_END))
+            continue
+        dwell += 1
+        if np.float32(s) > np.float32(thr * np.float32(dwell)):
+            count += 1
+            if count == int(tong_max_val):
+                state = TONG_POSITIVE
+        else:
+            count -= 1
+            if count == 0:
+                state = TONG_NEGATIVE
+        if dwell >= int(tong_max_dwells):
+            state = TONG_NEGATIVE
+        out.append((dwell, count, state))
+    return out
+
+
+def tong_threshold(pfa, vector_length, bins):
+    """calculate_threshold of the two Tong adapters (gps_l1_ca_pcps_tong_acquisition.cc:226-245,
+    galileo_e1_pcps_tong_ambiguous_acquisition.cc): the quantile of an exponential distribution
+    with lambda = vector_length at (1 - pfa)^(1 / ncells), ncells = vector_length * bins, pfa a
+    float, the power in double, the result cast to float."""
+    ncells = int(vector_length) * int(bins)
+    val = (1.0 - float(np.float32(pfa))) ** (1.0 / float(ncells))
+    return float(np.float32(-np.log1p(-val) / float(vector_length)))
 
 
 def quicksync_decide(records, threshold, bit_transition, max_dwells):

@@ -3,10 +3,12 @@
 #include "beidou_b1i_pcps_acquisition_mi355x.h"
 #include "galileo_e1_pcps_ambiguous_acquisition_mi355x.h"
 #include "galileo_e1_pcps_pair_acquisition_mi355x.h"
+#include "galileo_e1_pcps_tong_ambiguous_acquisition_mi355x.h"
 #include "gnss_tracking_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_mi355x.h"
 #include "gps_l1_ca_pcps_quicksync_acquisition_mi355x.h"
+#include "gps_l1_ca_pcps_tong_acquisition_mi355x.h"
 #include "gsdr.h"
 
 namespace gsdr_factory
@@ -35,6 +37,11 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
     if (implementation == "GPS_L1_CA_PCPS_QuickSync_Acquisition_MI355X")
         return std::make_unique<GpsL1CaPcpsQuickSyncAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);
+    if (implementation == "GPS_L1_CA_PCPS_Tong_Acquisition_MI355X")
+        return std::make_unique<GpsL1CaPcpsTongAcquisitionMI355X>(configuration, role, in_streams, out_streams, device);
+    if (implementation == "Galileo_E1_PCPS_Tong_Ambiguous_Acquisition_MI355X")
+        return std::make_unique<GalileoE1PcpsTongAmbiguousAcquisitionMI355X>(configuration, role, in_streams,
+            out_streams, device);
     if (implementation == "Galileo_E1_PCPS_Ambiguous_Acquisition_MI355X")
         return std::make_unique<GalileoE1PcpsAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);

@@ -619,6 +619,72 @@ int gsdr_acq_run_quicksync_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t f
  * Either output may be null. */
 int gsdr_acq_dump_quicksync(gsdr_acq* acq, const void* iq_host, float* rows_out, float* cand_out);
 
+/* ---- Tong acquisition: pcps_tong_acquisition_cc, the variable-dwell detector.  An item is
+ * N = fft_size samples.  Every item adds its |IFFT(FFT(x w_d) C)|^2 rows, scaled by
+ * 1 / (fn fn P) with fn = float(N) float(N) and P the item's own input power (:268, :283-285,
+ * :312-314), into a grid that lives for a whole sequence of items (:317); the statistic of an
+ * item is the maximum of the accumulated grid, taken by the first row, scanning upwards with
+ * strict '<' (:325), that holds it and the first index in that row (:320).  The Tong counter
+ * starts at tong_init_val, goes up when the statistic exceeds threshold * dwell_count and down
+ * otherwise, and ends the sequence positive at tong_max_val, negative at 0 and, whatever it
+ * said, negative once dwell_count reaches tong_max_dwells (:349-372).  The handle is an
+ * ordinary one created with consumed_samples == fft_size, max_dwells 1 and no
+ * bit_transition_flag; its num_doppler_bins must be set to the reference's row count,
+ * 2 doppler_max / doppler_step + 1 (:166-184).  Every active code slot runs a sequence of its
+ * own; the threshold is gsdr_acq_set_threshold's. */
+typedef struct gsdr_acq_tong_result
+{
+    uint32_t prn;
+    uint32_t doppler_index;   /* first row holding the accumulated grid's maximum */
+    uint32_t indext;          /* first index of the maximum in that row (:320) */
+    int32_t doppler_hz;       /* Acq_doppler_hz */
+    double acq_delay_samples; /* indext % samples_per_code (:328) */
+    uint64_t samplestamp;     /* the item's first sample: stamp0 + k N (the block adds N, :272) */
+    float mag;                /* d_mag = d_test_statistics: the accumulated grid's maximum */
+    float input_power;        /* d_input_power: sum |x|^2 / N of the item */
+    uint32_t dwell_count;     /* d_dwell_count after the item */
+    uint32_t tong_count;      /* d_tong_count after the item */
+    uint32_t state;           /* GSDR_TONG_* */
+    uint32_t pad;             /* 0 */
+} gsdr_acq_tong_result;
+
+#define GSDR_TONG_RUNNING 0  /* the sequence goes on */
+#define GSDR_TONG_POSITIVE 1 /* the item ended it: positive acquisition (state 2 of the block) */
+#define GSDR_TONG_NEGATIVE 2 /* the item ended it: negative acquisition (state 3 of the block) */
+#define GSDR_TONG_PAST_END 3 /* the item lies after the sequence's end and is no part of it: only prn,
+                              * samplestamp, input_power and the final counts are set */
+
+/* Makes the handle a Tong one and allocates the grid (max_prns x num_doppler_bins x fft_size
+ * floats), the slots' sequence state and the per-item scales and row maxima of max_blocks
+ * items; every slot starts as gsdr_acq_tong_reset leaves it.  GSDR_E_ARG unless
+ * 1 <= tong_init_val < tong_max_val and tong_max_dwells >= 1 (the reference's unsigned counter
+ * wraps from init 0, and init >= max never meets its '==').  GSDR_E_UNSUPPORTED for a handle
+ * with max_dwells > 1, bit_transition_flag or consumed_samples != fft_size, for an fft_size
+ * served by the four-step plans and while the carrier model is not GSDR_WIPE_EXACT.  An error
+ * leaves the handle as it was; plain runs on the handle are unaffected by a success too.  The
+ * codes are those of gsdr_acq_set_local_codes. */
+int gsdr_acq_set_tong(gsdr_acq* acq, uint32_t tong_init_val, uint32_t tong_max_val, uint32_t tong_max_dwells);
+/* set_state(1) for nslots code slots (slots null: all of them): counts back to their start,
+ * sequence running, and the slot's next item starts its rows from zero.  A slot >= max_prns is
+ * GSDR_E_ARG; GSDR_E_STATE before gsdr_acq_set_tong. */
+int gsdr_acq_tong_reset(gsdr_acq* acq, const uint32_t* slots, uint32_t nslots);
+/* nitems consecutive host items of fft_size samples of the handle's item type, continuing
+ * every slot's sequence from where the previous call left it; out [nitems][nprn] records.
+ * Items past a sequence's end, in this call or a later one, are GSDR_TONG_PAST_END until the
+ * slot is reset.  Synchronous, one stream synchronisation per call.  GSDR_E_STATE before
+ * gsdr_acq_set_tong or without plain codes; GSDR_E_UNSUPPORTED while the carrier model is not
+ * GSDR_WIPE_EXACT; nitems outside [1, max_blocks] is GSDR_E_ARG.  With gsdr_acq_set_profiling
+ * enabled the forward pass is recorded in stage [0], the grid kernel in [1] and the input
+ * powers and the counter kernel in [2]. */
+int gsdr_acq_run_tong(gsdr_acq* acq, const void* iq_host, uint32_t nitems, uint64_t stamp0,
+    gsdr_acq_tong_result* out);
+/* The same on the ring's samples from first_sample, read in place. */
+int gsdr_acq_run_tong_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_sample, uint32_t nitems,
+    uint64_t stamp0, gsdr_acq_tong_result* out_host);
+/* Debug/verification: the accumulated grid of a slot as it stands, [num_doppler_bins][fft_size]
+ * floats.  Rows of a slot that has seen no item since its reset are reported as zeros. */
+int gsdr_acq_dump_tong_grid(gsdr_acq* acq, uint32_t prn_slot, float* grid_host);
+
 /* ======================================================================== */
 /* Tracking multicorrelator (Cpu_Multicorrelator_Real_Codes / Cpu_Multicorrelator) */
 /* ======================================================================== */
