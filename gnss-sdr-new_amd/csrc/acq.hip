@@ -323,6 +323,7 @@ void gsdr_acq_destroy(gsdr_acq* a)
     pairs_free(a);
     quicksync_free(a);
     tong_free(a);
+    iqcaf_free(a);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     delete a;
 }
@@ -459,7 +460,7 @@ int gsdr_acq_run_device(gsdr_acq* a, const void* iq_dev, uint32_t nblocks, uint6
     gsdr_acq_result* out_dev, void* stream)
 {
     GSDR_REQUIRE(a && iq_dev && out_dev, GSDR_E_ARG, "gsdr_acq_run_device: null argument");
-    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_device: set_local_codes first");
+    GSDR_REQUIRE(a->nprn > 0 && a->slots != gsdr_acq::Slots::IqCaf, GSDR_E_STATE, "gsdr_acq_run_device: set_local_codes first");
     int rc = check_block_count(a, "gsdr_acq_run_device", nblocks, "nblocks");
     if (rc != GSDR_OK) return rc;
     GSDR_REQUIRE(stride >= a->consumed || nblocks == 1, GSDR_E_ARG, "gsdr_acq_run_device: block stride %llu < consumed %u",
@@ -473,7 +474,7 @@ int gsdr_acq_run_device(gsdr_acq* a, const void* iq_dev, uint32_t nblocks, uint6
 int gsdr_acq_run(gsdr_acq* a, const void* iq_host, uint32_t nblocks, uint64_t stamp0, gsdr_acq_result* out)
 {
     GSDR_REQUIRE(a && iq_host && out, GSDR_E_ARG, "gsdr_acq_run: null argument");
-    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run: set_local_codes first");
+    GSDR_REQUIRE(a->nprn > 0 && a->slots != gsdr_acq::Slots::IqCaf, GSDR_E_STATE, "gsdr_acq_run: set_local_codes first");
     int rc = check_block_count(a, "gsdr_acq_run", nblocks, "nblocks");
     if (rc != GSDR_OK) return rc;
     std::lock_guard<std::mutex> lk(a->mu);
@@ -489,7 +490,7 @@ int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, u
     gsdr_acq_result* out)
 {
     GSDR_REQUIRE(a && ring && out, GSDR_E_ARG, "gsdr_acq_run_stream: null argument");
-    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_stream: set_local_codes first");
+    GSDR_REQUIRE(a->nprn > 0 && a->slots != gsdr_acq::Slots::IqCaf, GSDR_E_STATE, "gsdr_acq_run_stream: set_local_codes first");
     int rc = check_block_count(a, "gsdr_acq_run_stream", nblocks, "nblocks");
     if (rc == GSDR_OK) rc = gsdr::check_ring_consumer("gsdr_acq_run_stream", ring, a->conf.item_type, a->device, "acquisition");
     if (rc != GSDR_OK) return rc;
@@ -503,7 +504,7 @@ int gsdr_acq_run_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, u
 int gsdr_acq_submit_stream(gsdr_acq* a, gsdr_stream* ring, uint64_t first_sample, uint32_t nblocks, uint64_t stamp0)
 {
     GSDR_REQUIRE(a && ring, GSDR_E_ARG, "gsdr_acq_submit_stream: null argument");
-    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_submit_stream: set_local_codes first");
+    GSDR_REQUIRE(a->nprn > 0 && a->slots != gsdr_acq::Slots::IqCaf, GSDR_E_STATE, "gsdr_acq_submit_stream: set_local_codes first");
     int rc = check_block_count(a, "gsdr_acq_submit_stream", nblocks, "nblocks");
     if (rc == GSDR_OK) rc = gsdr::check_ring_consumer("gsdr_acq_submit_stream", ring, a->conf.item_type, a->device, "acquisition");
     if (rc != GSDR_OK) return rc;
@@ -548,7 +549,7 @@ int gsdr_acq_collect(gsdr_acq* a, gsdr_acq_result* out, uint32_t* nblocks, uint3
 int gsdr_acq_run_dwell(gsdr_acq* a, const void* iq_host, uint32_t dwell, uint64_t stamp, gsdr_acq_result* out)
 {
     GSDR_REQUIRE(a && iq_host && out, GSDR_E_ARG, "gsdr_acq_run_dwell: null argument");
-    GSDR_REQUIRE(a->nprn > 0, GSDR_E_STATE, "gsdr_acq_run_dwell: set_local_codes first");
+    GSDR_REQUIRE(a->nprn > 0 && a->slots != gsdr_acq::Slots::IqCaf, GSDR_E_STATE, "gsdr_acq_run_dwell: set_local_codes first");
     GSDR_REQUIRE(dwell < a->conf.max_dwells, GSDR_E_ARG, "gsdr_acq_run_dwell: dwell %u outside [0,%u)", dwell,
         a->conf.max_dwells);
     std::lock_guard<std::mutex> lk(a->mu);

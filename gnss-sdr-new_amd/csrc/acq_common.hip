@@ -375,6 +375,8 @@ namespace gsdr_acq_impl
 //       plan) or one PRN per 512-lane workgroup (1, the default)
 //   GSDR_ACQ_CORR_VARIANT  a packed correlate variant (PkVariants, acq_pk.hip) other
 //       than default_pk_variant's, for tests
+//   GSDR_ACQ_IQCAF_ROWS_HBM=1  the IQ-CAF grid kernel's rows in device memory at every size
+//       (acq_iqcaf.hip), for comparing the two forms at one size
 AcqEnv read_acq_env()
 {
     AcqEnv e;
@@ -390,6 +392,7 @@ AcqEnv read_acq_env()
     e.qpw = env_int("GSDR_ACQ_QPW", GSDR_ACQ_QPW_DEFAULT);
     e.ppw = env_int("GSDR_ACQ_PPW", GSDR_ACQ_PPW_DEFAULT);
     e.corr_variant = env_int("GSDR_ACQ_CORR_VARIANT", -1);
+    e.iqcaf_rows_hbm = env_int("GSDR_ACQ_IQCAF_ROWS_HBM", 0) != 0;
     return e;
 }
 

@@ -17,6 +17,7 @@ struct AcqEnv
     bool xshift{true}, four_generic{false}, split{true}, split_arg{true};
     int qpw{0}, ppw{0};
     int corr_variant{-1};  // -1: default_pk_variant(N)
+    bool iqcaf_rows_hbm{false};
 };
 
 // ====================================================================== handle
@@ -56,12 +57,13 @@ struct gsdr_acq
     uint32_t* d_prn{nullptr};
     uint32_t nprn{0};
     // what the nprn active code slots hold (set_slots, called by every code setter):
-    // plain codes, nprn / 2 pairs or nprn folded QuickSync codes
+    // plain codes, nprn / 2 pairs, nprn folded QuickSync codes or iq.nslots slots per IQ-CAF satellite
     enum class Slots
     {
         Plain,
         Pairs,
-        QuickSync
+        QuickSync,
+        IqCaf
     } slots{Slots::Plain};
     float2* d_X{nullptr};
     gsdr_acq_impl::RowStat* d_stats{nullptr};
@@ -163,6 +165,21 @@ struct gsdr_acq
         gsdr_acq_impl::RowStat* d_stats{nullptr};   // max_blocks x max_prns x D row maxima of the accumulated rows
         gsdr_acq_tong_result* d_out{nullptr};       // max_blocks x max_prns records
     } tong;
+    // E5a non-coherent IQ acquisition with CAF filter (gsdr_acq_set_iq_caf / gsdr_acq_run_iq_caf,
+    // acq_iqcaf.hip): the buffers are built by gsdr_acq_set_iq_caf
+    struct IqCaf
+    {
+        uint32_t nslots{0};  // code slots per satellite: 1, 2 or 4 (> 0: configured)
+        uint32_t spc{0}, coherent_ms{0};
+        bool both{false};
+        int32_t window_hz{0};
+        bool rows_lds{false};  // the grid kernel keeps a workgroup's |.|^2 rows in LDS
+        float2* d_in{nullptr};    // the caller's rows: 2 x (max_prns / nslots) rows of N
+        float* d_rows{nullptr};   // rows in HBM: max_blocks x (max_prns / nslots) x D regions of nslots x N
+        float* d_power{nullptr};  // max_blocks input powers
+        gsdr_acq_iq_caf_row* d_rec{nullptr};     // max_blocks x (max_prns / nslots) x D row records
+        gsdr_acq_iq_caf_result* d_out{nullptr};  // max_blocks x (max_prns / nslots) records
+    } iq;
     std::mutex mu;
 };
 
@@ -198,6 +215,12 @@ struct AcqView
     const TongSlot* tong_slots{nullptr};
     RowStat* tong_stats{nullptr};
     bool tong_row_lds{false};
+    // an IQ-CAF run (AcqOp::IqCaf, acq_iqcaf.hip): nprn = iq_nslots x satellites; the row
+    // records, the HBM rows (null: the rows wait in LDS) and the slot layout
+    gsdr_acq_iq_caf_row* iq_rec{nullptr};
+    float* iq_rows{nullptr};
+    uint32_t iq_nslots{0};
+    bool iq_both{false}, iq_rows_lds{false};
 };
 
 // The operation of a per-plan dispatch, with the arguments each kind reads.
@@ -211,7 +234,9 @@ struct AcqOp
         DumpGrid,     // prn_slot
         SetAttrs,
         Dwell,        // dwell, stamp0, res, s
-        Tong          // iq, nblocks, stride, s (the view's tong_* fields)
+        Tong,         // iq, nblocks, stride, s (the view's tong_* fields)
+        IqCaf,        // iq, nblocks, stride, s (the view's iq_* fields)
+        IqCafAttrs    // the LDS attribute of the IQ-CAF grid kernel for the handle's iq settings
     } kind;
     const void* iq{nullptr};
     uint32_t nblocks{0};
@@ -230,6 +255,20 @@ inline bool tong_row_fits_lds(const gsdr_acq* a) { return a->lds_bytes + (size_t
 inline size_t tong_lds_bytes(const gsdr_acq* a)
 {
     return a->lds_bytes + (tong_row_fits_lds(a) ? (size_t)a->N * sizeof(float) : 0);
+}
+
+// Dynamic LDS of acq_iqcaf_grid_kernel on the handle's plan: behind the transform's buffer and
+// the statistics scratch a 64-byte stash of the slots' peaks, then the satellite's nslots rows of
+// N floats where that fits the limit (the four-step plans keep a word of static LDS besides).
+constexpr size_t kIqCafStash = 64;
+inline bool iqcaf_rows_fit_lds(const gsdr_acq* a, uint32_t nslots)
+{
+    return !a->env.iqcaf_rows_hbm &&
+           a->lds_bytes + kIqCafStash + (size_t)nslots * a->N * sizeof(float) + (a->variant >= 20 ? 16 : 0) <= kLdsBytes;
+}
+inline size_t iqcaf_lds_bytes(const gsdr_acq* a, uint32_t nslots, bool rows_lds)
+{
+    return a->lds_bytes + kIqCafStash + (rows_lds ? (size_t)nslots * a->N * sizeof(float) : 0);
 }
 
 // Default packed correlate variant for an FFT size (0: none, the generic kernels).
@@ -255,7 +294,7 @@ auto with_item_type(int it, F&& f)
 }
 constexpr int kItemTypes[] = {GSDR_ITEM_GR_COMPLEX, GSDR_ITEM_CSHORT, GSDR_ITEM_IBYTE};
 
-// The one statement of what the code slots hold, for the five code setters.
+// The one statement of what the code slots hold, for the code setters.
 inline void set_slots(gsdr_acq* a, gsdr_acq::Slots kind, uint32_t nprn)
 {
     a->slots = kind;
@@ -364,6 +403,8 @@ int quicksync_rebuild_wipeoffs(gsdr_acq* a);
 void quicksync_free(gsdr_acq* a);
 // acq_tong.hip: free the Tong buffers
 void tong_free(gsdr_acq* a);
+// acq_iqcaf.hip: free the IQ-CAF buffers
+void iqcaf_free(gsdr_acq* a);
 // acq.hip: the per-plan dispatch of an op, and the code spectra (with their lane-order
 // copies) of slots [first_slot, first_slot + nslots) from their staged codes
 int dispatch(gsdr_acq* a, const AcqView& v, const AcqOp& op);

@@ -3,6 +3,7 @@
 // which instantiates them for one group of acq_plans.h.
 #pragma once
 #include "acq_handle.h"
+#include "acq_iqcaf_kernels.h"
 #include "acq_plans.h"
 #include "acq_quicksync_kernels.h"
 #include "acq_tong_kernels.h"
@@ -311,6 +312,48 @@ int launch_tong(gsdr_acq* a, const AcqView& v, const AcqOp& op)
     return GSDR_OK;
 }
 
+// The IQ-CAF grid kernel's LDS attribute for the handle's settings (gsdr_acq_set_iq_caf).
+template <class PT>
+int set_iqcaf_attrs(const gsdr_acq* a)
+{
+    const size_t bytes = iqcaf_lds_bytes(a, a->iq.nslots, a->iq.rows_lds);
+    return a->iq.rows_lds ? set_max_lds((const void*)acq_iqcaf_grid_kernel<PT, true>, bytes)
+                          : set_max_lds((const void*)acq_iqcaf_grid_kernel<PT, false>, bytes);
+}
+
+// gsdr_acq_run_iq_caf: forward spectra of the nblocks items at op.iq -- the engine's own forward
+// pass, in two launches where the split path has its scratch -- and the grid kernel over them on
+// the view's IQ-CAF buffers, one workgroup per (row, satellite, item).
+template <class PT>
+int launch_iqcaf(gsdr_acq* a, const AcqView& v, const AcqOp& op)
+{
+    hipStream_t s = op.s;
+    StageTimer t(a, s);
+    t.begin();
+    bool two = false;
+    if constexpr (requires_subplan<PT>::value) two = a->d_fscratch != nullptr;
+    if constexpr (requires_subplan<PT>::value)
+        {
+            if (two) launch_forward_two<PT>(a, v, op.iq, op.nblocks, op.stride, s);
+        }
+    if (!two) launch_forward<PT>(a, v, op.iq, op.nblocks, op.stride, s);
+    GSDR_HIP(hipGetLastError());
+    t.end(0);
+    t.begin();
+    const uint32_t nsat = v.nprn / v.iq_nslots;
+    const dim3 grid(v.D * nsat, op.nblocks);
+    const size_t lds = iqcaf_lds_bytes(a, v.iq_nslots, v.iq_rows_lds);
+    if (v.iq_rows_lds)
+        hipLaunchKernelGGL((acq_iqcaf_grid_kernel<PT, true>), grid, dim3(PT::NT), lds, s, a->d_X, v.code_fft, v.iq_rec,
+            a->d_tw, plan_of<PT>(a), (float*)nullptr, v.D, nsat, v.iq_nslots, v.iq_both ? 1u : 0u, v.xm);
+    else
+        hipLaunchKernelGGL((acq_iqcaf_grid_kernel<PT, false>), grid, dim3(PT::NT), lds, s, a->d_X, v.code_fft, v.iq_rec,
+            a->d_tw, plan_of<PT>(a), v.iq_rows, v.D, nsat, v.iq_nslots, v.iq_both ? 1u : 0u, v.xm);
+    GSDR_HIP(hipGetLastError());
+    t.end(1);
+    return GSDR_OK;
+}
+
 // Code spectra of slots [first_slot, first_slot + nslots) from their staged codes.
 template <class PT>
 int launch_code_fft(gsdr_acq* a, const AcqOp& op)
@@ -360,6 +403,8 @@ int run_op(gsdr_acq* a, const AcqView& v, const AcqOp& op)
                 return launch_tong<PT>(a, v, op);
             else
                 break;
+        case AcqOp::IqCaf: return launch_iqcaf<PT>(a, v, op);
+        case AcqOp::IqCafAttrs: return set_iqcaf_attrs<PT>(a);
         }
     return GSDR_E_STATE;
 }

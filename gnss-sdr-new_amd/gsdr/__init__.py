@@ -59,6 +59,8 @@ EXPORTED = [
     "gsdr_acq_run_quicksync_stream", "gsdr_acq_dump_quicksync",
     "gsdr_acq_set_tong", "gsdr_acq_tong_reset", "gsdr_acq_run_tong", "gsdr_acq_run_tong_stream",
     "gsdr_acq_dump_tong_grid",
+    "gsdr_acq_set_iq_caf", "gsdr_acq_set_iq_codes", "gsdr_acq_run_iq_caf", "gsdr_acq_run_iq_caf_stream",
+    "gsdr_acq_dump_iq_caf_rows",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -314,6 +316,49 @@ assert all(ACQ_TONG_RESULT_DTYPE.fields[f][1] == getattr(AcqTongResult, f).offse
 TONG_RUNNING, TONG_POSITIVE, TONG_NEGATIVE, TONG_PAST_END = 0, 1, 2, 3
 
 
+class AcqIqCafRow(ctypes.Structure):
+    """gsdr_acq_iq_caf_row: one (satellite, Doppler row) of gsdr_acq_dump_iq_caf_rows."""
+    _fields_ = [
+        ("choice_i", ctypes.c_uint32),
+        ("choice_q", ctypes.c_uint32),
+        ("peak_i", ctypes.c_float),
+        ("peak_q", ctypes.c_float),
+        ("sum_peak", ctypes.c_float),
+        ("sum_index", ctypes.c_uint32),
+    ]
+
+
+class AcqIqCafResult(ctypes.Structure):
+    """gsdr_acq_iq_caf_result: one (item, satellite) outcome of gsdr_acq_run_iq_caf."""
+    _fields_ = [
+        ("prn", ctypes.c_uint32),
+        ("doppler_index", ctypes.c_uint32),
+        ("caf_doppler_index", ctypes.c_uint32),
+        ("indext", ctypes.c_uint32),
+        ("doppler_hz", ctypes.c_int32),
+        ("caf_doppler_hz", ctypes.c_int32),
+        ("mag", ctypes.c_float),
+        ("input_power", ctypes.c_float),
+        ("test_statistic", ctypes.c_float),
+        ("pad", ctypes.c_float),
+        ("acq_delay_samples", ctypes.c_double),
+        ("samplestamp", ctypes.c_uint64),
+    ]
+
+
+ACQ_IQ_CAF_ROW_DTYPE = np.dtype([
+    ("choice_i", np.uint32), ("choice_q", np.uint32), ("peak_i", np.float32), ("peak_q", np.float32),
+    ("sum_peak", np.float32), ("sum_index", np.uint32)])
+ACQ_IQ_CAF_RESULT_DTYPE = np.dtype([
+    ("prn", np.uint32), ("doppler_index", np.uint32), ("caf_doppler_index", np.uint32), ("indext", np.uint32),
+    ("doppler_hz", np.int32), ("caf_doppler_hz", np.int32), ("mag", np.float32), ("input_power", np.float32),
+    ("test_statistic", np.float32), ("pad", np.float32), ("acq_delay_samples", np.float64),
+    ("samplestamp", np.uint64)])
+for _dt, _st in ((ACQ_IQ_CAF_ROW_DTYPE, AcqIqCafRow), (ACQ_IQ_CAF_RESULT_DTYPE, AcqIqCafResult)):
+    assert _dt.itemsize == ctypes.sizeof(_st)
+    assert all(_dt.fields[f][1] == getattr(_st, f).offset for f, _ in _st._fields_)
+
+
 class CorrJob(ctypes.Structure):
     _fields_ = [
         ("channel", ctypes.c_int32),
@@ -393,6 +438,12 @@ def load():
         L.gsdr_acq_run_tong.argtypes = [P, P, U32, U64, P]
         L.gsdr_acq_run_tong_stream.argtypes = [P, P, U64, U32, U64, P]
         L.gsdr_acq_dump_tong_grid.argtypes = [P, U32, P]
+    if hasattr(L, "gsdr_acq_set_iq_caf"):  # (as above)
+        L.gsdr_acq_set_iq_caf.argtypes = [P, U32, U32, I, ctypes.c_int32]
+        L.gsdr_acq_set_iq_codes.argtypes = [P, P, P, P, U32]
+        L.gsdr_acq_run_iq_caf.argtypes = [P, P, U32, U64, P]
+        L.gsdr_acq_run_iq_caf_stream.argtypes = [P, P, U64, U32, U64, P]
+        L.gsdr_acq_dump_iq_caf_rows.argtypes = [P, P, P]
     L.gsdr_corr_create.argtypes = [I, I, I, I, P]
     L.gsdr_corr_destroy.argtypes = [P]
     L.gsdr_corr_destroy.restype = None
@@ -918,6 +969,99 @@ class Acquisition:
         g = np.zeros((self.num_doppler_bins, self.fft_size), np.float32)
         _check(load().gsdr_acq_dump_tong_grid(self._h, int(prn_slot), _ptr(g)))
         return g
+
+    # ---- E5a non-coherent IQ with CAF filter (galileo_e5a_noncoherent_iq_acquisition_caf_cc)
+    def set_iq_caf(self, samples_per_code, coherent_ms=1, both_components=False, caf_window_hz=0):
+        """gsdr_acq_set_iq_caf: the handle serves run_iq_caf from now on.  coherent_ms 1 to 3 (1 for
+        the zero-padded form); a satellite takes (2 if coherent_ms > 1 else 1) * (2 if
+        both_components else 1) code slots of max_prns."""
+        _check(load().gsdr_acq_set_iq_caf(self._h, int(samples_per_code), int(coherent_ms), int(bool(both_components)),
+                                          int(caf_window_hz)))
+        self.iq_both = bool(both_components)
+        self.iq_nsat = 0
+
+    def set_iq_codes(self, code_i, code_q, prns):
+        """gsdr_acq_set_iq_codes: code_i / code_q = [nsat, fft_size] complex64, the rows the
+        adapter hands to set_local_code (tiled coherent_ms times or zero padded); code_q is None
+        with one component."""
+        prns = np.ascontiguousarray(prns, np.uint32)
+        code_i = np.ascontiguousarray(code_i, np.complex64)
+        assert code_i.shape == (len(prns), self.fft_size), code_i.shape
+        if code_q is not None:
+            code_q = np.ascontiguousarray(code_q, np.complex64)
+            assert code_q.shape == code_i.shape, code_q.shape
+        _check(load().gsdr_acq_set_iq_codes(self._h, _ptr(code_i), None if code_q is None else _ptr(code_q),
+                                            _ptr(prns), len(prns)))
+        self.iq_nsat = len(prns)
+
+    def run_iq_caf(self, iq, nitems=1, stamp0=0, first_sample=0):
+        """gsdr_acq_run_iq_caf: nitems host items of fft_size samples, each a grid of its own,
+        or, with a Stream for iq, gsdr_acq_run_iq_caf_stream on its items from first_sample ->
+        structured array [nitems, nsat] (ACQ_IQ_CAF_RESULT_DTYPE); iq_caf_decide applies the
+        dwell rule."""
+        nsat = getattr(self, "iq_nsat", 0)
+        out = np.zeros(nitems * max(nsat, 1), ACQ_IQ_CAF_RESULT_DTYPE)
+        if isinstance(iq, Stream):
+            _check(load().gsdr_acq_run_iq_caf_stream(self._h, iq._h, int(first_sample), int(nitems), int(stamp0),
+                                                     _ptr(out)))
+            return out.reshape(nitems, -1)
+        iq = self._items(iq)
+        need = nitems * self.fft_size * (1 if int(self.item_type) == ITEM_GR_COMPLEX else 2)
+        assert iq.size >= need, (iq.size, need)
+        _check(load().gsdr_acq_run_iq_caf(self._h, _ptr(iq), int(nitems), int(stamp0), _ptr(out)))
+        return out.reshape(nitems, -1)
+
+    def dump_iq_caf_rows(self, iq):
+        """gsdr_acq_dump_iq_caf_rows: the row records of one item, structured array
+        [nsat, num_doppler_bins] (ACQ_IQ_CAF_ROW_DTYPE)."""
+        iq = self._items(iq)
+        nsat = getattr(self, "iq_nsat", 0)
+        out = np.zeros((max(nsat, 1), self.num_doppler_bins), ACQ_IQ_CAF_ROW_DTYPE)
+        _check(load().gsdr_acq_dump_iq_caf_rows(self._h, _ptr(iq), _ptr(out)))
+        return out
+
+
+def iq_caf_decide(records, threshold, bit_transition, max_dwells, caf_filter=False):
+    """The dwell rule of galileo_e5a_noncoherent_iq_acquisition_caf_cc (:258-271, :549-568,
+    :669-700) on one satellite's records, one per dwell in order (a column of run_iq_caf) ->
+    (synchro, positive, num_dwells), synchro a dict of acq_delay_samples, acq_doppler_hz,
+    acq_samplestamp_samples, doppler_index and test_statistics as they stand after the last dwell
+    read.
+
+    d_test_statistics is zeroed when the attempt starts and never between its dwells; d_mag is
+    zeroed at every dwell, so every dwell has a winner of its own.  That winner takes over the
+    synchro fields and the statistic when not bit_transition, or when the statistic so far is
+    strictly below the dwell's (:559); a dwell whose grid is all zeros has no winner.  With the
+    filter on (caf_filter) every dwell's CAF Doppler overwrites acq_doppler_hz whether or not its
+    winner took over (:672).  The dwell that reaches max_dwells decides: test_statistics >
+    threshold (:686-696).  positive is None when the records end before that."""
+    records = np.asarray(records)
+    assert records.dtype == ACQ_IQ_CAF_RESULT_DTYPE and records.ndim == 1 and len(records) > 0
+    thr = np.float32(threshold)
+    syn = {"acq_delay_samples": 0.0, "acq_doppler_hz": 0.0, "acq_samplestamp_samples": 0, "doppler_index": 0,
+           "test_statistics": np.float32(0.0)}
+    for k in range(len(records)):
+        rec = records[k]
+        stat = np.float32(rec["test_statistic"])
+        if np.float32(rec["mag"]) > np.float32(0.0) and (not bit_transition or syn["test_statistics"] < stat):
+            syn["acq_delay_samples"] = float(rec["acq_delay_samples"])
+            syn["acq_doppler_hz"] = float(rec["doppler_hz"])
+            syn["acq_samplestamp_samples"] = int(rec["samplestamp"])
+            syn["doppler_index"] = int(rec["doppler_index"])
+            syn["test_statistics"] = stat
+        if caf_filter:
+            syn["acq_doppler_hz"] = float(rec["caf_doppler_hz"])
+        if k + 1 == int(max_dwells):
+            return syn, bool(syn["test_statistics"] > thr), k + 1
+    return syn, None, len(records)
+
+
+def iq_caf_threshold(pfa, vector_length, doppler_max, doppler_step):
+    """GalileoE5aNoncoherentIQAcquisitionCaf::calculate_threshold (adapter :274-291): the formula
+    of tong_threshold with the inclusive row count of -doppler_max .. doppler_max."""
+    assert int(doppler_step) > 0
+    bins = len(range(-int(doppler_max), int(doppler_max) + 1, int(doppler_step)))
+    return tong_threshold(pfa, vector_length, bins)
 
 
 def tong_decide(stats, threshold, tong_init_val, tong_max_val, tong_max_dwells):

@@ -4,6 +4,7 @@
 #include "galileo_e1_pcps_ambiguous_acquisition_mi355x.h"
 #include "galileo_e1_pcps_pair_acquisition_mi355x.h"
 #include "galileo_e1_pcps_tong_ambiguous_acquisition_mi355x.h"
+#include "galileo_e5a_noncoherent_iq_acquisition_caf_mi355x.h"
 #include "gnss_tracking_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_mi355x.h"
@@ -51,6 +52,13 @@ std::unique_ptr<AcquisitionInterface> GetAcqBlock(const ConfigurationInterface* 
     if (implementation == "Galileo_E1_PCPS_8ms_Ambiguous_Acquisition_MI355X")
         return std::make_unique<GalileoE1Pcps8msAmbiguousAcquisitionMI355X>(configuration, role, in_streams, out_streams,
             device);
+    if (implementation == "Galileo_E5a_Noncoherent_IQ_Acquisition_CAF_MI355X")
+        {
+            // the E5a primary codes come from the user's table: no block without one (throws, with the reason)
+            GalileoE5aNoncoherentIQAcquisitionCafMI355X::load_code_table(configuration, role);
+            return std::make_unique<GalileoE5aNoncoherentIQAcquisitionCafMI355X>(configuration, role, in_streams,
+                out_streams, device);
+        }
     if (implementation == "BEIDOU_B1I_PCPS_Acquisition_MI355X")
         return std::make_unique<BeidouB1iPcpsAcquisitionMI355X>(configuration, role, in_streams, out_streams, device);
     return nullptr;

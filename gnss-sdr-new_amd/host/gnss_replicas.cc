@@ -5,6 +5,7 @@
 #include <bitset>
 #include <cmath>
 #include <cstring>
+#include <fstream>
 #include <string>
 
 namespace
@@ -226,6 +227,83 @@ std::vector<std::complex<float>> galileo_e1_code_gen_complex_sampled(const char*
     std::vector<std::complex<float>> dest(re.size());
     for (size_t i = 0; i < re.size(); i++) dest[i] = std::complex<float>(re[i], 0.0F);
     return dest;
+}
+
+// ======================================================================= Galileo E5a
+namespace
+{
+std::vector<uint8_t>& e5a_table()
+{
+    static std::vector<uint8_t> table;
+    return table;
+}
+}  // namespace
+
+bool galileo_e5a_load_code_table(const std::string& path, std::string* error)
+{
+    const auto refuse = [&](const std::string& why) {
+        if (error) *error = "Galileo E5a code table '" + path + "': " + why;
+        return false;
+    };
+    if (path.empty()) return refuse("no file named");
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) return refuse("cannot be read");
+    const auto size = static_cast<long long>(f.tellg());
+    if (size != static_cast<long long>(kGalileoE5aTableBytes))
+        return refuse("has " + std::to_string(size) + " bytes, a table has " + std::to_string(kGalileoE5aTableBytes) +
+                      " (100 rows of 10230 bits, each padded to 1279 bytes)");
+    std::vector<uint8_t> t(kGalileoE5aTableBytes);
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(t.data()), static_cast<std::streamsize>(t.size()));
+    if (!f) return refuse("cannot be read");
+    e5a_table() = std::move(t);
+    return true;
+}
+
+bool galileo_e5a_code_table_loaded() { return !e5a_table().empty(); }
+
+std::vector<std::complex<float>> galileo_e5_a_code_gen_complex_primary(int32_t prn, const char* signal)
+{
+    const auto& t = e5a_table();
+    if (t.empty() || prn < 1 || prn > 50 || !signal || signal[0] != '5') return {};
+    const char comp = signal[1];
+    if (comp != 'I' && comp != 'Q' && comp != 'X') return {};
+    const uint8_t* row_i = t.data() + static_cast<size_t>(prn - 1) * kGalileoE5aRowBytes;
+    const uint8_t* row_q = row_i + 50 * static_cast<size_t>(kGalileoE5aRowBytes);
+    const auto chip = [](const uint8_t* row, uint32_t i) { return ((row[i >> 3] >> (7 - (i & 7))) & 1U) ? -1.0F : 1.0F; };
+    std::vector<std::complex<float>> dest(kGalileoE5aCodeLengthChips);
+    for (uint32_t i = 0; i < kGalileoE5aCodeLengthChips; i++)
+        {
+            if (comp == 'X')
+                dest[i] = std::complex<float>(chip(row_i, i), chip(row_q, i));
+            else
+                dest[i] = std::complex<float>(chip(comp == 'I' ? row_i : row_q, i), 0.0F);
+        }
+    return dest;
+}
+
+bool galileo_e5_a_code_gen_complex_sampled(std::vector<std::complex<float>>& dest, uint32_t prn, const char* signal,
+    int32_t sampling_freq, uint32_t chip_shift)
+{
+    constexpr uint32_t code_length = kGalileoE5aCodeLengthChips;
+    constexpr int32_t code_freq_basis = 10230000;  // GALILEO_E5A_CODE_CHIP_RATE_CPS
+    const auto samples_per_code = static_cast<uint32_t>(
+        static_cast<double>(sampling_freq) / (static_cast<double>(code_freq_basis) / static_cast<double>(code_length)));
+    const uint32_t delay = ((code_length - chip_shift) % code_length) * samples_per_code / code_length;
+    auto code = galileo_e5_a_code_gen_complex_primary(static_cast<int32_t>(prn), signal);
+    if (code.empty() || samples_per_code == 0 || dest.size() < samples_per_code) return false;
+    if (sampling_freq != code_freq_basis)
+        {
+            // the resampler picks source indices alone: the same ones for both parts
+            std::vector<float> re(code.size()), im(code.size());
+            for (size_t i = 0; i < code.size(); i++) re[i] = code[i].real(), im[i] = code[i].imag();
+            re = resample(re, samples_per_code, static_cast<float>(code_freq_basis), static_cast<float>(sampling_freq));
+            im = resample(im, samples_per_code, static_cast<float>(code_freq_basis), static_cast<float>(sampling_freq));
+            code.resize(samples_per_code);
+            for (uint32_t i = 0; i < samples_per_code; i++) code[i] = std::complex<float>(re[i], im[i]);
+        }
+    for (uint32_t i = 0; i < samples_per_code; i++) dest[(i + delay) % samples_per_code] = code[i];
+    return true;
 }
 
 // ======================================================================= BeiDou B1I

@@ -1,12 +1,14 @@
 // Code replica generators used on the acquisition / tracking hot path:
 // GPS L1 C/A (src/algorithms/libs/gps_sdr_signal_replica.cc:25-176),
-// Galileo E1 OS (src/algorithms/libs/galileo_e1_signal_replica.cc:29-233) and
+// Galileo E1 OS (src/algorithms/libs/galileo_e1_signal_replica.cc:29-233), Galileo E5a
+// (src/algorithms/libs/galileo_e5_signal_replica.cc:31-124) and
 // BeiDou B1I (src/algorithms/libs/beidou_b1i_signal_replica.cc:26-176).
 #ifndef GSDR_HOST_GNSS_REPLICAS_H
 #define GSDR_HOST_GNSS_REPLICAS_H
 
 #include <complex>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 // +1 / -1 chips of GPS L1 C/A for PRN 1-32 and SBAS 120-138 (empty on a bad PRN).
@@ -35,6 +37,28 @@ std::vector<float> galileo_e1_code_gen_float_sampled(const char* signal, bool cb
 // galileo_e1_code_gen_complex_sampled (:213-233): the same as real part, imaginary 0
 std::vector<std::complex<float>> galileo_e1_code_gen_complex_sampled(const char* signal, bool cboc, uint32_t prn,
     int32_t sampling_freq, uint32_t chip_shift = 0, bool secondary_flag = false);
+
+// ---- Galileo E5a (E5a-I data "5I", E5a-Q pilot "5Q", both "5X") ----
+// The primary codes (Galileo OS SIS ICD Annex C: 50 PRNs x 10230 chips per component) are
+// data the user supplies at run time; the repository ships no table.  The file holds 100 rows
+// of 10230 bits, PRN 1-50 of E5a-I and then PRN 1-50 of E5a-Q, each row MSB first and padded
+// to kGalileoE5aRowBytes bytes; a set bit is the chip -1 (hex_to_binary_converter: bit 0 -> +1).
+constexpr uint32_t kGalileoE5aCodeLengthChips = 10230;
+constexpr uint32_t kGalileoE5aRowBytes = 1279;
+constexpr size_t kGalileoE5aTableBytes = 100 * static_cast<size_t>(kGalileoE5aRowBytes);
+// Reads the table for the generators below; false, with the reason in *error, unless the file
+// can be read and has exactly kGalileoE5aTableBytes bytes (the table in effect then stays).
+bool galileo_e5a_load_code_table(const std::string& path, std::string* error = nullptr);
+bool galileo_e5a_code_table_loaded();
+// galileo_e5_a_code_gen_complex_primary (galileo_e5_signal_replica.cc:31-96): one sample per
+// chip; "5I" and "5Q" real-valued rows, "5X" I + jQ.  Empty on a bad PRN or signal, or
+// without a table.
+std::vector<std::complex<float>> galileo_e5_a_code_gen_complex_primary(int32_t prn, const char* signal);
+// galileo_e5_a_code_gen_complex_sampled (:99-124): dest[0, fs / 1000) gets one code period
+// sampled at fs with the float resampler the E1 path has, circularly delayed by chip_shift
+// chips; false (dest untouched) where the primary code is empty or dest is too short.
+bool galileo_e5_a_code_gen_complex_sampled(std::vector<std::complex<float>>& dest, uint32_t prn, const char* signal,
+    int32_t sampling_freq, uint32_t chip_shift = 0);
 
 // ---- BeiDou B1I ----
 // beidou_b1i_code_gen_int (:26-106): +1 / -1 chips of PRN 1-63 (2046 chips; empty on a bad PRN)

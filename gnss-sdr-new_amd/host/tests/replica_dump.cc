@@ -4,6 +4,9 @@
 // Usage: replica_dump <kind> <prn> [fs] [cboc] [secondary]
 //   kind: gps_float | gps_sampled | gal_b_sinboc11 | gal_c_sinboc11 | gal_b_sampled |
 //         gal_c_sampled | bds_float | bds_sampled
+//        replica_dump e5a_i | e5a_q | e5a_x <prn> <fs> <chip shift> <code table>
+//   (tests/test_host_e5a_replicas.py; exit 3 with the loader's message on stderr where the table
+//   is refused, 4 where the generator gives no code)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +42,22 @@ int main(int argc, char** argv)
         {
             const auto v = galileo_e1_code_gen_complex_sampled(kind[4] == 'b' ? "1B" : "1C", cboc,
                 static_cast<uint32_t>(prn), fs, 0, sec);
+            return put(v.data(), v.size() * 8);
+        }
+    if (kind == "e5a_i" || kind == "e5a_q" || kind == "e5a_x")
+        {
+            if (argc < 6) return 2;
+            std::string why;
+            if (!galileo_e5a_load_code_table(argv[5], &why))
+                {
+                    std::fprintf(stderr, "%s\n", why.c_str());
+                    return 3;
+                }
+            const char signal[3] = {'5', static_cast<char>(kind[4] - 'a' + 'A'), '\0'};
+            std::vector<std::complex<float>> v(static_cast<size_t>(fs / 1000));
+            if (!galileo_e5_a_code_gen_complex_sampled(v, static_cast<uint32_t>(prn), signal, fs,
+                    static_cast<uint32_t>(std::atoi(argv[4]))))
+                return 4;
             return put(v.data(), v.size() * 8);
         }
     if (kind == "bds_float")

@@ -685,6 +685,80 @@ int gsdr_acq_run_tong_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_
  * floats.  Rows of a slot that has seen no item since its reset are reported as zeros. */
 int gsdr_acq_dump_tong_grid(gsdr_acq* acq, uint32_t prn_slot, float* grid_host);
 
+/* ---- E5a non-coherent IQ acquisition with CAF filter:
+ * galileo_e5a_noncoherent_iq_acquisition_caf_cc.  An item is N = fft_size samples.  Every Doppler
+ * row correlates the data replica (I) and, with both components, the pilot replica (Q); with 2 or
+ * 3 ms of coherent integration also the B form of each, the replica with its first code period
+ * negated (:186-205).  Per component the form with the larger normalised peak is chosen ('>=': A
+ * keeps a tie, :455, :464) -- the reference reads the Q-B peak from the I-B row (:445), which is
+ * kept -- and the two chosen |.|^2 rows are added cell by cell; the maximum of the sum is the
+ * row's value (:470-546).  The answer of the grid is the first row, scanning upwards with strict
+ * '<' (:549), that holds the maximum.  With caf_window_hz > 0 the chosen components' raw peaks
+ * over the rows pass the weighted window of :599-668, whose first maximum names the Doppler the
+ * block reports (:670-672).  The handle is an ordinary one created with consumed_samples ==
+ * fft_size, max_dwells 1 and no bit_transition_flag; its num_doppler_bins must be set to the
+ * reference's row count, 2 doppler_max / doppler_step + 1 (:227-232).  Every item of a call is a
+ * grid of its own; the dwell rule over the items' records (:549-568, :686-700) is the caller's. */
+typedef struct gsdr_acq_iq_caf_row
+{
+    uint32_t choice_i;        /* 0: the I-A row was chosen, 1: I-B (:455) */
+    uint32_t choice_q;        /* 0: Q-A, 1: Q-B (:464); 0 with one component */
+    float peak_i;             /* d_CAF_vector_I: the chosen I row's own raw maximum */
+    float peak_q;             /* d_CAF_vector_Q: the chosen Q row's own raw maximum (Q-B's true one); 0 with one component */
+    float sum_peak;           /* raw maximum of the summed row (of the chosen I row with one component) */
+    uint32_t sum_index;       /* its first index */
+} gsdr_acq_iq_caf_row;
+
+typedef struct gsdr_acq_iq_caf_result
+{
+    uint32_t prn;
+    uint32_t doppler_index;     /* first row holding the grid maximum (:549) */
+    uint32_t caf_doppler_index; /* first maximum of d_CAF_vector (:670); == doppler_index with the filter off */
+    uint32_t indext;            /* first index of the maximum in the winning row's sum */
+    int32_t doppler_hz;         /* the grid winner's Doppler (:562) */
+    int32_t caf_doppler_hz;     /* the filter's Doppler (:671); == doppler_hz with the filter off */
+    float mag;                  /* d_mag: the maximum / (fn fn), fn = float(N) float(N), in float (:373, :488) */
+    float input_power;          /* d_input_power: sum |x|^2 / N of the item (:385-387) */
+    float test_statistic;       /* mag / input_power (:566) */
+    float pad;                  /* 0 */
+    double acq_delay_samples;   /* indext % samples_per_code (:561) */
+    uint64_t samplestamp;       /* the item's first sample: stamp0 + k N */
+} gsdr_acq_iq_caf_result;
+
+/* Makes the handle an IQ-CAF one and allocates what the runs need (the caller's replica rows,
+ * the rows' records and the results of max_blocks items, and the |.|^2 rows of a workgroup
+ * where they do not fit its LDS).  coherent_ms is 1 to 3 (1 also for the zero-padded form: the
+ * block then holds only the A forms, :104-107); a satellite takes 1, 2 or 4 code slots (I-A, I-B
+ * when coherent_ms > 1, Q-A when both_components, Q-B when both hold), and max_prns bounds slots
+ * x satellites.  GSDR_E_ARG for samples_per_code 0 or > fft_size, coherent_ms outside [1,3], and
+ * where the reference would divide by zero or index outside its vectors: caf_window_hz > 0 with
+ * caf_window_hz / (2 doppler_step) == 0 or with 2 (caf_window_hz / (2 doppler_step)) + 1 >
+ * num_doppler_bins.  GSDR_E_UNSUPPORTED for a handle with max_dwells > 1, bit_transition_flag or
+ * consumed_samples != fft_size and while the carrier model is not GSDR_WIPE_EXACT.  Every FFT plan
+ * is served.  GSDR_ACQ_IQCAF_ROWS_HBM=1 (read at create) keeps the workgroup's rows in device
+ * memory at every size.  An error leaves the handle as it was. */
+int gsdr_acq_set_iq_caf(gsdr_acq* acq, uint32_t samples_per_code, uint32_t coherent_ms, int both_components,
+    int32_t caf_window_hz);
+/* The replicas of nsat satellites as the adapter hands them to set_local_code (:160): code_i and
+ * code_q are nsat rows of fft_size complex<float>, already tiled coherent_ms times or zero padded;
+ * code_q is null with one component (and must not be with both).  The B forms are made on the
+ * device and every slot is transformed as gsdr_acq_set_local_codes transforms its rows.  The handle
+ * holds IQ-CAF codes -- plain runs are GSDR_E_STATE -- until another code setter is called.
+ * GSDR_E_STATE before gsdr_acq_set_iq_caf; nsat = 0 or slots x nsat > max_prns is GSDR_E_ARG. */
+int gsdr_acq_set_iq_codes(gsdr_acq* acq, const float* code_i, const float* code_q, const uint32_t* prn, uint32_t nsat);
+/* nitems host items of fft_size samples of the handle's item type, fft_size apart; out
+ * [nitems][nsat] records, fetched in one read-back.  Synchronous.  GSDR_E_STATE before both set
+ * calls; nitems outside [1, max_blocks] is GSDR_E_ARG.  With gsdr_acq_set_profiling enabled the
+ * forward pass is recorded in stage [0], the grid kernel in [1] and the input powers and the
+ * finish kernel in [2]. */
+int gsdr_acq_run_iq_caf(gsdr_acq* acq, const void* iq_host, uint32_t nitems, uint64_t stamp0,
+    gsdr_acq_iq_caf_result* out);
+/* The same on the ring's samples from first_sample, read in place. */
+int gsdr_acq_run_iq_caf_stream(gsdr_acq* acq, gsdr_stream* stream, uint64_t first_sample, uint32_t nitems,
+    uint64_t stamp0, gsdr_acq_iq_caf_result* out_host);
+/* Debug/verification: the row records of one item, out [nsat][num_doppler_bins]. */
+int gsdr_acq_dump_iq_caf_rows(gsdr_acq* acq, const void* iq_host, gsdr_acq_iq_caf_row* out);
+
 /* ======================================================================== */
 /* Tracking multicorrelator (Cpu_Multicorrelator_Real_Codes / Cpu_Multicorrelator) */
 /* ======================================================================== */
