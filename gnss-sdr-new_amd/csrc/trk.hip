@@ -31,6 +31,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "fft_pk.h"
@@ -91,6 +92,19 @@ constexpr double kBdsB1Period = 0.001;
 constexpr int kBdsB1Length = 2046;
 constexpr const char* kBdsB1Nh = "00000100110101001110";
 constexpr const char* kBdsB1GeoPreamble = "1111110000001100001100";
+// Galileo E5a (Galileo_E5a.h:30-39, :3581) and GPS L5 (GPS_L5.h:30-45, :167-172)
+constexpr double kGalE5aHz = 1.17645e9;
+constexpr double kGalE5aRate = 1.023e7;
+constexpr double kGalE5aPeriod = 0.001;
+constexpr int kGalE5aLength = 10230;
+constexpr const char* kGalE5aISecondary = "10000100001011101001";
+constexpr int kGalE5aQSecondaryLength = 100;
+constexpr double kGpsL5Hz = 1.17645e9;
+constexpr double kGpsL5Rate = 1.023e7;
+constexpr double kGpsL5Period = 0.001;
+constexpr int kGpsL5Length = 10230;
+constexpr const char* kGpsL5iNh = "0000110101";
+constexpr const char* kGpsL5qNh = "00000100110101001110";
 constexpr const char* kGpsCaPreamble =
     "1111111111111111111100000000000000000000000000000000000000000000000000000000000011111111111111111111000000000000"
     "000000001111111111111111111111111111111111111111";
@@ -246,6 +260,7 @@ struct TrkConst
     SmConst sm[2];  // 0: CN0, 1: carrier lock test
     CfConst cf_narrow;
     int32_t high_dyn, smoother_length;  // Dll_Pll_Conf::high_dyn / smoother_length (dll_pll_conf.h:62,80)
+    int32_t interchange_iq;  // d_interchange_iq (:242, :310): Prompt_I / Prompt_Q swapped on output
 };
 
 // Mutable scalar loop state (dll_pll_veml_tracking.h:117-209 minus the
@@ -980,8 +995,8 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
             if (t.current_data_symbol == 0)
                 {
                     log_point(c, t, o);
-                    o.prompt_i = (double)t.P_data_accu.x;
-                    o.prompt_q = (double)t.P_data_accu.y;
+                    o.prompt_i = (double)(c.interchange_iq ? t.P_data_accu.y : t.P_data_accu.x);  // :2001-2010
+                    o.prompt_q = (double)(c.interchange_iq ? t.P_data_accu.x : t.P_data_accu.y);
                     o.flags |= GSDR_TRK_F_VALID_OUTPUT;
                     t.P_data_accu = make_float2(0.f, 0.f);
                 }
@@ -1009,8 +1024,8 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
                     if (t.current_data_symbol == 0)
                         {
                             log_point(c, t, o);
-                            o.prompt_i = (double)t.P_data_accu.x;
-                            o.prompt_q = (double)t.P_data_accu.y;
+                            o.prompt_i = (double)(c.interchange_iq ? t.P_data_accu.y : t.P_data_accu.x);  // :2054-2063
+                            o.prompt_q = (double)(c.interchange_iq ? t.P_data_accu.x : t.P_data_accu.y);
                             o.flags |= GSDR_TRK_F_VALID_OUTPUT;
                             t.P_data_accu = make_float2(0.f, 0.f);
                         }
@@ -1103,6 +1118,16 @@ __device__ __forceinline__ uintptr_t stream_fetch(const void* iq, uint64_t iq_by
     return start;
 }
 
+// the two f16 halves of a compact replica word (gathered as float bits), widened (exact)
+__device__ __forceinline__ float half_lo(float w)
+{
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)(__float_as_uint(w) & 0xffffu));
+}
+__device__ __forceinline__ float half_hi(float w)
+{
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)(__float_as_uint(w) >> 16));
+}
+
 // (int)floorf(x) in one instruction (v_cvt_flr_i32_f32: floor, then convert; exact)
 __device__ __forceinline__ int floor_i(float x)
 {
@@ -1136,7 +1161,14 @@ __device__ __forceinline__ ChunkNco chunk_nco(const Prep& p)
 // DATA: one more accumulator, acc[kMaxTrkTaps], on the data-component replica
 // s_data at the prompt tap's index (the pilot-tracking data correlator of
 // do_correlation_step, whose only tap sits at the prompt shift).
-template <int IT, int SRC, int WRAP, bool FULL, int KT, bool DATA, int SPL = kSpl>
+// PACK: the compact replica (pilot tracking of the 10230-chip signals): one LDS
+// word per code index, the pilot chip as an f16 in its low half and the data
+// chip in its high half (s_code points at the words, s_data is unused).  The
+// data chip comes out of the prompt tap's word, so the call has no data gather;
+// each gathered word costs one v_cvt_f32_f16 more (KT + 1 per sample).  The host
+// packs only values an f16 holds exactly, so the converted floats, the FMAs and
+// the sums are those of the float layout.
+template <int IT, int SRC, int WRAP, bool FULL, int KT, bool DATA, int SPL = kSpl, bool PACK = false>
 __device__ __forceinline__ void correlate_chunk(const void* __restrict__ iq, const float2* s_win, const float* s_code,
     const float* s_data, const Prep& p, const ChunkNco& q, int n0, int vl, int L, const float (&sh_rem)[kMaxTrkTaps], float2& ph,
     float2 (&acc)[kMaxTrkTaps + 1], const char* sbuf = nullptr, int sboff = 0)
@@ -1192,7 +1224,7 @@ __device__ __forceinline__ void correlate_chunk(const void* __restrict__ iq, con
                     cv[j][k] = __int_as_float(raw);
                 }
         }
-    if (DATA)
+    if (DATA && !PACK)
         {
             // first: the data replica is gathered at the prompt tap's index
 #pragma unroll
@@ -1205,6 +1237,16 @@ __device__ __forceinline__ void correlate_chunk(const void* __restrict__ iq, con
             for (int j = 0; j < SPL; ++j) cv[j][k] = s_code[__float_as_int(cv[j][k])];
         }
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PACK)
+        {
+#pragma unroll
+            for (int j = 0; j < SPL; ++j)
+                {
+                    if (DATA) dv[j] = half_hi(cv[j][IPK]);
+#pragma unroll
+                    for (int k = 0; k < KT; ++k) cv[j][k] = half_lo(cv[j][k]);
+                }
+        }
     c2 tt[SPL];
     c2 phv = gsdr::pk::from(ph);
 #pragma unroll
@@ -1233,7 +1275,7 @@ __device__ __forceinline__ void correlate_chunk(const void* __restrict__ iq, con
 }
 
 // the chunk at n0 with the call's wrap mode; FULL when the whole chunk is inside the call
-template <int IT, int SRC, int KT, bool DATA, int SPL>
+template <int IT, int SRC, int KT, bool DATA, int SPL, bool PACK>
 __device__ __forceinline__ void correlate_chunk_wrap(const void* __restrict__ iq, const float2* s_win, const float* s_code,
     const float* s_data, const Prep& p, const ChunkNco& q, int n0, int vl, int L, const float (&sh_rem)[kMaxTrkTaps], float2& ph,
     float2 (&acc)[kMaxTrkTaps + 1], const char* sbuf, int sboff)
@@ -1241,17 +1283,17 @@ __device__ __forceinline__ void correlate_chunk_wrap(const void* __restrict__ iq
     if (q.wrap == 2)
         {
             if (SPL == kSpl && n0 + kWinCore <= vl)
-                correlate_chunk<IT, SRC, 2, true, KT, DATA, SPL>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
+                correlate_chunk<IT, SRC, 2, true, KT, DATA, SPL, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
                     sbuf, sboff);
             else
-                correlate_chunk<IT, SRC, 2, false, KT, DATA, SPL>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
+                correlate_chunk<IT, SRC, 2, false, KT, DATA, SPL, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
                     sbuf, sboff);
         }
     else if (q.wrap == 1)
-        correlate_chunk<IT, SRC, 1, false, KT, DATA, SPL>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf,
+        correlate_chunk<IT, SRC, 1, false, KT, DATA, SPL, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf,
             sboff);
     else
-        correlate_chunk<IT, SRC, 0, false, KT, DATA, SPL>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf,
+        correlate_chunk<IT, SRC, 0, false, KT, DATA, SPL, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf,
             sboff);
 }
 
@@ -1259,20 +1301,20 @@ __device__ __forceinline__ void correlate_chunk_wrap(const void* __restrict__ iq
 // samples per lane as cover it (1, 2, 4 or kSpl): a 25000-sample call's last 424
 // samples take one sample per lane instead of a full chunk of masked ones.  The
 // samples and their order are those of the full chunk (a masked sample adds 0).
-template <int IT, int SRC, int KT, bool DATA>
+template <int IT, int SRC, int KT, bool DATA, bool PACK = false>
 __device__ __forceinline__ void correlate_chunk_any(const void* __restrict__ iq, const float2* s_win, const float* s_code,
     const float* s_data, const Prep& p, const ChunkNco& q, int n0, int vl, int L, const float (&sh_rem)[kMaxTrkTaps], float2& ph,
     float2 (&acc)[kMaxTrkTaps + 1], const char* sbuf = nullptr, int sboff = 0)
 {
     const int rest = vl - n0;
     if (rest >= kWinCore || rest > 4 * kTrkThreads || kSpl <= 4)
-        correlate_chunk_wrap<IT, SRC, KT, DATA, kSpl>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
+        correlate_chunk_wrap<IT, SRC, KT, DATA, kSpl, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
     else if (rest > 2 * kTrkThreads)
-        correlate_chunk_wrap<IT, SRC, KT, DATA, 4>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
+        correlate_chunk_wrap<IT, SRC, KT, DATA, 4, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
     else if (rest > kTrkThreads)
-        correlate_chunk_wrap<IT, SRC, KT, DATA, 2>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
+        correlate_chunk_wrap<IT, SRC, KT, DATA, 2, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
     else
-        correlate_chunk_wrap<IT, SRC, KT, DATA, 1>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
+        correlate_chunk_wrap<IT, SRC, KT, DATA, 1, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc, sbuf, sboff);
 }
 
 // high_dyn correlation (do_correlation_step with set_high_dynamics_resampler(true)):
@@ -1328,7 +1370,7 @@ __device__ __forceinline__ void correlate_call_hd(const void* __restrict__ iq, c
         }
 }
 
-template <int IT, int KT, bool DATA>
+template <int IT, int KT, bool DATA, bool PACK = false>
 __device__ __forceinline__ void correlate_call(const void* __restrict__ iq, const float2* s_win, const float* s_code,
     const float* s_data, const Prep& p, int vl, int L, const float (&sh_rem)[kMaxTrkTaps], float2& ph,
     float2 (&acc)[kMaxTrkTaps + 1])
@@ -1337,9 +1379,9 @@ __device__ __forceinline__ void correlate_call(const void* __restrict__ iq, cons
     for (int n0 = 0; n0 < vl; n0 += kWinCore)
         {
             if (p.woff >= 0)
-                correlate_chunk_any<IT, 0, KT, DATA>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc);
+                correlate_chunk_any<IT, 0, KT, DATA, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc);
             else
-                correlate_chunk_any<IT, 1, KT, DATA>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc);
+                correlate_chunk_any<IT, 1, KT, DATA, PACK>(iq, s_win, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc);
         }
 }
 
@@ -1349,7 +1391,7 @@ __device__ __forceinline__ void correlate_call(const void* __restrict__ iq, cons
 // prefetched during the previous call's loop update when `pf_ok` (else fetched
 // here).  The __syncthreads at the top of each chunk drains the DMA (vmcnt(0))
 // and orders the previous chunk's reads before its buffer is refilled.
-template <int IT, int KT, bool DATA>
+template <int IT, int KT, bool DATA, bool PACK = false>
 __device__ __forceinline__ void correlate_call_stream(const void* __restrict__ iq, uint64_t iq_items, char* sb,
     int sbuf_bytes, int chunk, bool pf_ok, const uintptr_t (&pf_start)[2], const float* s_code, const float* s_data, const Prep& p,
     int vl, int L, const float (&sh_rem)[kMaxTrkTaps], float2& ph, float2 (&acc)[kMaxTrkTaps + 1], bool probe, uint64_t& swait)
@@ -1406,7 +1448,7 @@ __device__ __forceinline__ void correlate_call_stream(const void* __restrict__ i
                         }
                     else
                         {
-                            correlate_chunk_any<IT, 2, KT, DATA>(iq, nullptr, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
+                            correlate_chunk_any<IT, 2, KT, DATA, PACK>(iq, nullptr, s_code, s_data, p, q, n0, vl, L, sh_rem, ph, acc,
                                 buf, boff);
                             n0 += kWinCore;
                         }
@@ -1499,14 +1541,17 @@ __device__ __forceinline__ Prep make_prep(const TrkConst& c, const TrkHot& t, bo
 // sit in LDS.  While wave 0 runs the loop update of call e, every lane fetches
 // the samples call e+1 will most likely read (the consumed count is one code
 // period +-1 sample), so the update hides the HBM latency.
-template <int IT>
+// PACK: every channel of the launch tracks a pilot on the compact replica (see
+// correlate_chunk); the handle launches it instead when its replicas qualify.
+template <int IT, bool PACK = false>
 __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __restrict__ consts,
     TrkChan* __restrict__ chans, const float* const* __restrict__ codes, const float* const* __restrict__ data_codes,
     const void* __restrict__ iq, uint64_t iq_first, uint64_t iq_items, uint32_t max_epochs, gsdr_trk_epoch* __restrict__ out,
     uint32_t* __restrict__ nout, int code_pad, int data_pad, uint64_t* __restrict__ timing, int timing_wall, int stream_chunk,
     int sbuf_bytes)
 {
-    // LDS: [replica | data replica (pilot tracking) | next call's input window]
+    // LDS: [replica | data replica (pilot tracking) | next call's input window];
+    // PACK: [compact replica (pilot and data chips) | next call's input window], data_pad = 0
     extern __shared__ float s_dyn[];
     // replicas with kCodeMargin wrapped samples on each side: s_code[-M .. L+M)
     float* s_code = s_dyn + kCodeMargin;
@@ -1577,11 +1622,26 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
     const bool data = c.track_pilot != 0;
     {
         const float* cd = codes[ch];
-        for (int i = tid - kCodeMargin; i < L + kCodeMargin; i += kTrkThreads) s_code[i] = cd[((i % L) + L) % L];
-        if (data)
+        if constexpr (PACK)
             {
                 const float* dd = data_codes[ch];
-                for (int i = tid - kCodeMargin; i < L + kCodeMargin; i += kTrkThreads) s_data[i] = dd[((i % L) + L) % L];
+                for (int i = tid - kCodeMargin; i < L + kCodeMargin; i += kTrkThreads)
+                    {
+                        const int m = ((i % L) + L) % L;
+                        const uint32_t lo = __builtin_bit_cast(unsigned short, (_Float16)cd[m]);
+                        const uint32_t hi = __builtin_bit_cast(unsigned short, (_Float16)dd[m]);
+                        s_code[i] = __uint_as_float(lo | (hi << 16));
+                    }
+            }
+        else
+            {
+                for (int i = tid - kCodeMargin; i < L + kCodeMargin; i += kTrkThreads) s_code[i] = cd[((i % L) + L) % L];
+                if (data)
+                    {
+                        const float* dd = data_codes[ch];
+                        for (int i = tid - kCodeMargin; i < L + kCodeMargin; i += kTrkThreads)
+                            s_data[i] = dd[((i % L) + L) % L];
+                    }
             }
     }
     int64_t win_base = INT64_MIN;  // absolute-index base of the staged window (uniform)
@@ -1641,7 +1701,22 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
 #pragma unroll
             for (int k = 0; k < kMaxTrkTaps; ++k)
                 sh_rem[k] = gsdr::sub_rn(p.narrow ? c.shifts_narrow[k] : c.shifts[k], p.rem_code);
-            if (p.hd)
+            if constexpr (PACK)
+                {
+                    // pilot tracking without high_dyn (the host launches this kernel for nothing else)
+                    const bool sw = timing && tid == 0;
+                    if (streamed && K <= 3)
+                        correlate_call_stream<IT, 3, true, true>(iq, iq_items, s_sb, sbuf_bytes, stream_chunk, p.pf_ok, pf_start,
+                            s_code, s_data, p, vl, L, sh_rem, ph, acc, sw, swait);
+                    else if (streamed)
+                        correlate_call_stream<IT, kMaxTrkTaps, true, true>(iq, iq_items, s_sb, sbuf_bytes, stream_chunk, p.pf_ok,
+                            pf_start, s_code, s_data, p, vl, L, sh_rem, ph, acc, sw, swait);
+                    else if (K <= 3)
+                        correlate_call<IT, 3, true, true>(iq, s_win, s_code, s_data, p, vl, L, sh_rem, ph, acc);
+                    else
+                        correlate_call<IT, kMaxTrkTaps, true, true>(iq, s_win, s_code, s_data, p, vl, L, sh_rem, ph, acc);
+                }
+            else if (p.hd)
                 {
                     const float* sk = p.narrow ? c.shifts_narrow : c.shifts;
                     correlate_call_hd<IT>(iq, s_win, s_code, s_data, p, vl, L, K, data, sk[0], sk[c.iP], acc);
@@ -2149,6 +2224,13 @@ struct gsdr_trk
     std::vector<float*> data_code_bufs;  // pilot tracking: data-component replicas
     float** d_data_codes{nullptr};
     std::vector<int> data_code_len;
+    // per-channel pilot secondary code (gsdr_trk_set_secondary_code: Galileo E5a-Q)
+    std::vector<std::string> sec_codes;
+    // compact replicas: asked for (5X / L5 pilot handles, GSDR_TRK_PACK_REPLICAS=1), whether each
+    // channel's two replicas are exact in f16, and whether the launches use the compact kernel
+    bool pack_wanted{false};
+    std::vector<char> code_f16, data_f16;
+    bool pack{false};
     gsdr_trk_epoch* d_out{nullptr};
     uint32_t* d_nout{nullptr};
     uint32_t out_cap{0};
@@ -2276,6 +2358,8 @@ SignalParams signal_params(int signal)
 {
     if (signal == GSDR_SIGNAL_GAL_1B) return {kGalE1Hz, kGalE1Period, kGalE1Rate, kGalE1Length, 2, 1, 1};
     if (signal == GSDR_SIGNAL_BDS_B1) return {kBdsB1Hz, kBdsB1Period, kBdsB1Rate, kBdsB1Length, 1, 20, 0};
+    if (signal == GSDR_SIGNAL_GAL_5X) return {kGalE5aHz, kGalE5aPeriod, kGalE5aRate, kGalE5aLength, 1, 20, 0};  // :289-319
+    if (signal == GSDR_SIGNAL_GPS_L5) return {kGpsL5Hz, kGpsL5Period, kGpsL5Rate, kGpsL5Length, 1, 10, 0};      // :210-244
     return {kGpsL1Hz, kGpsCaPeriod, kGpsCaRate, kGpsCaLength, 1, kGpsCaSymbolsPerBit, 0};
 }
 
@@ -2308,6 +2392,42 @@ void init_channel(const gsdr_trk_conf& cf, TrkConst& c, TrkChan& ch)
             code_registers(kBdsB1Nh, 20, reg, bits);
             c.data_sec_len = 20;
             c.data_sec_str = bits[0];
+        }
+    else if (cf.signal == GSDR_SIGNAL_GAL_5X)
+        {
+            c.track_pilot = cf.track_pilot ? 1 : 0;
+            c.secondary = 1;
+            uint32_t reg[5], bits[5];
+            code_registers(kGalE5aISecondary, 20, reg, bits);
+            if (c.track_pilot)
+                {
+                    // the E5a-Q secondary code is the PRN's (gsdr_trk_start, :703); the
+                    // E5a-I one is wiped from the data prompt (:306-310)
+                    c.sec_len = kGalE5aQSecondaryLength;
+                    c.data_sec_len = 20;
+                    c.data_sec_str = bits[0];
+                    c.interchange_iq = 1;
+                }
+            else
+                set_secondary(c, kGalE5aISecondary, 20);  // d_data_secondary_code_length stays 0 (:312-317)
+        }
+    else if (cf.signal == GSDR_SIGNAL_GPS_L5)
+        {
+            c.track_pilot = cf.track_pilot ? 1 : 0;
+            c.secondary = 1;
+            if (c.track_pilot)
+                {
+                    set_secondary(c, kGpsL5qNh, 20);  // :224-234
+                    uint32_t reg[5], bits[5];
+                    code_registers(kGpsL5iNh, 10, reg, bits);
+                    c.data_sec_len = 10;
+                    c.data_sec_str = bits[0];
+                }
+            else
+                {
+                    set_secondary(c, kGpsL5iNh, 10);  // :236-243
+                    c.interchange_iq = 1;
+                }
         }
     else
         set_secondary(c, kGpsCaPreamble, kPreambleLen);
@@ -2366,6 +2486,14 @@ int ensure_out(gsdr_trk* k, uint32_t max_epochs)
     return GSDR_OK;
 }
 
+// every value survives the round trip through f16 (the compact replica's halves)
+bool f16_exact(const float* v, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (!((float)(_Float16)v[i] == v[i])) return false;
+    return true;
+}
+
 // Dynamic LDS of a launch: the replica and the input window, padded up to a whole
 // CU's LDS so that no workgroup of another kernel (the acquisition grid on the
 // other queue) can share the CU with a tracking workgroup -- the loop is a
@@ -2405,6 +2533,16 @@ size_t lds_for(int code_pad, int data_pad)
     return std::max(need, reserve);
 }
 
+// the kernel instance of an item type and replica layout
+using TrkKernel = void (*)(const TrkConst*, TrkChan*, const float* const*, const float* const*, const void*, uint64_t, uint64_t,
+    uint32_t, gsdr_trk_epoch*, uint32_t*, int, int, uint64_t*, int, int, int);
+TrkKernel trk_kernel_of(int item_type, bool pack)
+{
+    if (item_type == GSDR_ITEM_GR_COMPLEX) return pack ? trk_kernel<GSDR_ITEM_GR_COMPLEX, true> : trk_kernel<GSDR_ITEM_GR_COMPLEX>;
+    if (item_type == GSDR_ITEM_CSHORT) return pack ? trk_kernel<GSDR_ITEM_CSHORT, true> : trk_kernel<GSDR_ITEM_CSHORT>;
+    return pack ? trk_kernel<GSDR_ITEM_IBYTE, true> : trk_kernel<GSDR_ITEM_IBYTE>;
+}
+
 int launch(gsdr_trk* k, const void* iq, uint64_t iq_first, uint64_t iq_items, uint32_t max_epochs, gsdr_trk_epoch* out,
     uint32_t* nout, hipStream_t s)
 {
@@ -2440,18 +2578,10 @@ int launch(gsdr_trk* k, const void* iq, uint64_t iq_first, uint64_t iq_items, ui
     const dim3 grid(k->conf.max_channels);
     int chunk = 0, sbuf = 0;
     stream_plan(k->lds_bytes, k->code_pad, k->data_pad, (int)gsdr::item_bytes(k->conf.item_type), chunk, sbuf);
-    if (k->conf.item_type == GSDR_ITEM_GR_COMPLEX)
-        hipLaunchKernelGGL((trk_kernel<GSDR_ITEM_GR_COMPLEX>), grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
-            (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out,
-            nout, k->code_pad, k->data_pad, timing, k->timing_wall, chunk, sbuf);
-    else if (k->conf.item_type == GSDR_ITEM_CSHORT)
-        hipLaunchKernelGGL((trk_kernel<GSDR_ITEM_CSHORT>), grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
-            (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out,
-            nout, k->code_pad, k->data_pad, timing, k->timing_wall, chunk, sbuf);
-    else
-        hipLaunchKernelGGL((trk_kernel<GSDR_ITEM_IBYTE>), grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
-            (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out,
-            nout, k->code_pad, k->data_pad, timing, k->timing_wall, chunk, sbuf);
+    const TrkKernel kern = trk_kernel_of(k->conf.item_type, k->pack);
+    hipLaunchKernelGGL(kern, grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
+        (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out, nout,
+        k->code_pad, k->data_pad, timing, k->timing_wall, chunk, sbuf);
     GSDR_HIP(hipGetLastError());
     GSDR_HIP(hipEventRecord(k->last_launch, s));
     if (k->profiling)
@@ -2512,7 +2642,7 @@ int gsdr_trk_create(int device, const gsdr_trk_conf* conf, gsdr_trk** out)
     *out = nullptr;
     GSDR_REQUIRE(conf->fs_in > 0.0, GSDR_E_ARG, "gsdr_trk_create: fs_in must be > 0");
     GSDR_REQUIRE(conf->max_channels > 0, GSDR_E_ARG, "gsdr_trk_create: max_channels must be > 0");
-    GSDR_REQUIRE(conf->signal >= GSDR_SIGNAL_GPS_1C && conf->signal <= GSDR_SIGNAL_BDS_B1, GSDR_E_UNSUPPORTED,
+    GSDR_REQUIRE(conf->signal >= GSDR_SIGNAL_GPS_1C && conf->signal <= GSDR_SIGNAL_GPS_L5, GSDR_E_UNSUPPORTED,
         "gsdr_trk_create: signal %d not implemented", conf->signal);
     GSDR_REQUIRE(conf->item_type >= GSDR_ITEM_GR_COMPLEX && conf->item_type <= GSDR_ITEM_IBYTE, GSDR_E_ARG,
         "gsdr_trk_create: unknown item type %d", conf->item_type);
@@ -2535,7 +2665,14 @@ int gsdr_trk_create(int device, const gsdr_trk_conf* conf, gsdr_trk** out)
     k->device = device;
     k->conf = *conf;
     // GPS L1 C/A and BeiDou B1I force track_pilot off (dll_pll_veml_tracking.cc:183, :402)
-    if (k->conf.signal != GSDR_SIGNAL_GAL_1B) k->conf.track_pilot = 0;
+    // Galileo E1, E5a and GPS L5 honour it (:210-244, :258-319)
+    if (k->conf.signal != GSDR_SIGNAL_GAL_1B && k->conf.signal != GSDR_SIGNAL_GAL_5X && k->conf.signal != GSDR_SIGNAL_GPS_L5)
+        k->conf.track_pilot = 0;
+    {
+        const char* pe = std::getenv("GSDR_TRK_PACK_REPLICAS");
+        const bool wide = k->conf.signal == GSDR_SIGNAL_GAL_5X || k->conf.signal == GSDR_SIGNAL_GPS_L5;
+        k->pack_wanted = k->conf.track_pilot && !k->conf.high_dyn && (wide || (pe && std::atoi(pe) != 0));
+    }
     {
         // the adapters' vector_length = round(fs_in / (chip rate / code length))
         const SignalParams sp = signal_params(k->conf.signal);
@@ -2549,6 +2686,9 @@ int gsdr_trk_create(int device, const gsdr_trk_conf* conf, gsdr_trk** out)
     k->code_bufs.assign(nch, nullptr);
     k->data_code_bufs.assign(nch, nullptr);
     k->data_code_len.assign(nch, 0);
+    k->sec_codes.assign(nch, std::string());
+    k->code_f16.assign(nch, 1);
+    k->data_f16.assign(nch, 1);
     k->code_pad = 1024 + 2 * kCodeMargin;  // grows with the longest replica started (gsdr_trk_start)
     k->data_pad = 0;
     k->lds_bytes = lds_for(k->code_pad, k->data_pad);
@@ -2583,6 +2723,10 @@ int gsdr_trk_create(int device, const gsdr_trk_conf* conf, gsdr_trk** out)
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)trk_kernel<GSDR_ITEM_IBYTE>, hipFuncAttributeMaxDynamicSharedMemorySize,
             (int)(kCuLds - kStaticLdsMargin));
+    // and the compact instance this handle can launch beside those
+    if (k->pack_wanted && e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)trk_kernel_of(k->conf.item_type, true),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kCuLds - kStaticLdsMargin));
     if (e != hipSuccess)
         {
             gsdr::set_error("gsdr_trk_create: %s", hipGetErrorString(e));
@@ -2676,6 +2820,9 @@ int gsdr_trk_start(gsdr_trk* k, int ch, uint32_t prn, const float* code, int cod
     GSDR_REQUIRE(!k->conf.track_pilot || k->data_code_len[ch] == code_samples, GSDR_E_STATE,
         "gsdr_trk_start: pilot tracking needs gsdr_trk_set_data_code with %d samples for channel %d first", code_samples,
         ch);
+    const bool e5a_pilot = k->conf.signal == GSDR_SIGNAL_GAL_5X && k->conf.track_pilot;
+    GSDR_REQUIRE(!e5a_pilot || !k->sec_codes[ch].empty(), GSDR_E_STATE,
+        "gsdr_trk_start: E5a pilot tracking needs gsdr_trk_set_secondary_code for channel %d first", ch);
     std::lock_guard<std::mutex> lk(k->mu);
     gsdr::DeviceGuard g(k->device);
     // the device copy is authoritative between launches (the loop runs there)
@@ -2710,6 +2857,8 @@ int gsdr_trk_start(gsdr_trk* k, int ch, uint32_t prn, const float* code, int cod
                     c.data_sec_str = bits[0];
                 }
         }
+    // d_secondary_code_string = GALILEO_E5A_Q_SECONDARY_CODE[PRN - 1] (:703), here the caller's
+    if (e5a_pilot) set_secondary(c, k->sec_codes[ch].data(), (int)k->sec_codes[ch].size());
     c.code_samples = code_samples;
     c.acq_sample_stamp = acq_samplestamp;
     double acq_code_phase_samples = acq_delay_samples;
@@ -2779,11 +2928,17 @@ int gsdr_trk_start(gsdr_trk* k, int ch, uint32_t prn, const float* code, int cod
     *first_sample = t.next_sample;
     {
         const int cp = std::max(k->code_pad, (code_samples + 2 * kCodeMargin + 1) & ~1);
-        const int dp = k->conf.track_pilot ? cp : 0;
+        // the compact form only when every channel's two replicas are exact in it;
+        // otherwise the float layout and its fit check
+        k->code_f16[ch] = f16_exact(code, code_samples);
+        bool pack = k->pack_wanted;
+        for (uint32_t i = 0; i < k->conf.max_channels; ++i) pack = pack && k->code_f16[i] && k->data_f16[i];
+        const int dp = k->conf.track_pilot && !pack ? cp : 0;
         GSDR_REQUIRE(lds_for(cp, dp) <= kCuLds - kStaticLdsMargin, GSDR_E_UNSUPPORTED,
             "gsdr_trk_start: replica of %d samples does not fit the LDS next to the input window", code_samples);
         k->code_pad = cp;
         k->data_pad = dp;
+        k->pack = pack;
     }
     k->lds_bytes = lds_for(k->code_pad, k->data_pad);
     GSDR_HIP(hipMemcpyAsync(k->code_bufs[ch], code, (size_t)code_samples * sizeof(float), hipMemcpyHostToDevice,
@@ -2807,6 +2962,22 @@ int gsdr_trk_set_data_code(gsdr_trk* k, int ch, const float* data_code, int code
         hipMemcpyHostToDevice, k->stream));
     GSDR_HIP(hipStreamSynchronize(k->stream));
     k->data_code_len[ch] = code_samples;
+    k->data_f16[ch] = f16_exact(data_code, code_samples);
+    return GSDR_OK;
+}
+
+int gsdr_trk_set_secondary_code(gsdr_trk* k, int ch, const char* bits, int len)
+{
+    GSDR_REQUIRE(k && bits, GSDR_E_ARG, "gsdr_trk_set_secondary_code: null argument");
+    GSDR_REQUIRE(ch >= 0 && ch < (int)k->conf.max_channels, GSDR_E_ARG, "gsdr_trk_set_secondary_code: channel %d", ch);
+    GSDR_REQUIRE(k->conf.signal == GSDR_SIGNAL_GAL_5X && k->conf.track_pilot, GSDR_E_STATE,
+        "gsdr_trk_set_secondary_code: only a Galileo E5a pilot handle takes a per-channel secondary code");
+    GSDR_REQUIRE(len >= 1 && len <= kPreambleLen, GSDR_E_ARG, "gsdr_trk_set_secondary_code: length %d outside [1,%d]", len,
+        kPreambleLen);
+    for (int i = 0; i < len; ++i)
+        GSDR_REQUIRE(bits[i] == '0' || bits[i] == '1', GSDR_E_ARG, "gsdr_trk_set_secondary_code: character %d is not 0 / 1", i);
+    std::lock_guard<std::mutex> lk(k->mu);
+    k->sec_codes[ch].assign(bits, (size_t)len);
     return GSDR_OK;
 }
 

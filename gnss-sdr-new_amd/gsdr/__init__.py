@@ -61,12 +61,15 @@ EXPORTED = [
     "gsdr_acq_dump_tong_grid",
     "gsdr_acq_set_iq_caf", "gsdr_acq_set_iq_codes", "gsdr_acq_run_iq_caf", "gsdr_acq_run_iq_caf_stream",
     "gsdr_acq_dump_iq_caf_rows",
+    "gsdr_trk_set_secondary_code",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
 SIGNAL_GPS_1C = 0
 SIGNAL_GAL_1B = 1
 SIGNAL_BDS_B1 = 2
+SIGNAL_GAL_5X = 3
+SIGNAL_GPS_L5 = 4
 TRK_F_VALID_OUTPUT, TRK_F_LOSS_OF_LOCK, TRK_F_PLL_180, TRK_F_BIT_SYNC, TRK_F_OVERRUN, TRK_F_LOGGED = 1, 2, 4, 8, 16, 32
 
 # include/gsdr.h gsdr_trk_conf / gsdr_trk_epoch (C layout)
@@ -475,6 +478,7 @@ def load():
     L.gsdr_host_register.argtypes = [P, ctypes.c_size_t]
     L.gsdr_host_unregister.argtypes = [P]
     L.gsdr_trk_set_data_code.argtypes = [P, I, P, I]
+    L.gsdr_trk_set_secondary_code.argtypes = [P, I, ctypes.c_char_p, I]
     L.gsdr_trk_run_device.argtypes = [P, P, U64, U64, U32, P, P, P]
     L.gsdr_trk_run.argtypes = [P, P, U64, U64, U32, P, P]
     L.gsdr_trk_get_channel.argtypes = [P, I, P, P, P, P]
@@ -1278,10 +1282,20 @@ class Tracking:
         except Exception:
             pass
 
-    def start(self, ch, prn, code, acq_delay_samples, acq_doppler_hz, acq_samplestamp, nitems_read, data_code=None):
+    def set_secondary_code(self, ch, bits):
+        """The PRN's pilot secondary code of channel ch as a '0'/'1' string (Galileo E5a
+        pilot tracking: the 100-chip E5a-Q code), before start()."""
+        b = bits.encode() if isinstance(bits, str) else bytes(bits)
+        _check(load().gsdr_trk_set_secondary_code(self._h, int(ch), b, len(b)))
+
+    def start(self, ch, prn, code, acq_delay_samples, acq_doppler_hz, acq_samplestamp, nitems_read, data_code=None,
+              secondary_code=None):
         """start_tracking + the state-1 pull-in call; data_code: the data component's
-        replica for pilot tracking (Galileo E1 with track_pilot)."""
+        replica for pilot tracking (Galileo E1, E5a, GPS L5 with track_pilot);
+        secondary_code: see set_secondary_code."""
         code = np.ascontiguousarray(code, np.float32)
+        if secondary_code is not None:
+            self.set_secondary_code(ch, secondary_code)
         if data_code is not None:
             dc = np.ascontiguousarray(data_code, np.float32)
             _check(load().gsdr_trk_set_data_code(self._h, int(ch), _ptr(dc), len(dc)))

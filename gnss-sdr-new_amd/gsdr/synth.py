@@ -328,3 +328,81 @@ def bds_b1i_iq(fs, n_samples, sats, seed_offset=0, noise=True, dtype=np.complex6
     if noise:
         out += (rng.standard_normal(n_samples) + 1j * rng.standard_normal(n_samples)) * np.sqrt(0.5)
     return out.astype(dtype)
+
+
+# ---------------------------------------------------------------- Galileo E5a, GPS L5
+# 10230-chip, 10.23 Mcps signals with a data component on I and a pilot on Q, each
+# times its own secondary code.  The primary chips come from the caller (the E5a
+# memory codes are a user file; any +-1 replica serves a tracking test).
+WIDEBAND_HZ = 1.17645e9
+GAL_E5A_I_SECONDARY = "10000100001011101001"
+GPS_L5I_NH = "0000110101"
+GPS_L5Q_NH = "00000100110101001110"
+
+
+class WidebandSatellite:
+    """code_i / code_q: the 10230 +-1 primary chips of the data / pilot component;
+    sec_q: the pilot's secondary code as a '0'/'1' string (E5a-Q: 100 chips per PRN;
+    ignored by l5_iq, whose pilot carries the 20-chip NH code)."""
+
+    def __init__(self, prn, doppler_hz, code_delay_chips, code_i, code_q, sec_q=None, cn0_dbhz=45.0, phase=0.0):
+        self.prn, self.doppler_hz, self.code_delay_chips = prn, doppler_hz, code_delay_chips
+        self.code_i, self.code_q = np.asarray(code_i, np.float64), np.asarray(code_q, np.float64)
+        self.sec_q, self.cn0_dbhz, self.phase = sec_q, cn0_dbhz, phase
+
+    def data_bits(self, nbits):
+        return np.where(np.random.default_rng(SEED + 37 * self.prn).random(nbits) < 0.5, -1.0, 1.0)
+
+
+def _sec_signs(s):
+    return np.array([1.0 if c == "0" else -1.0 for c in s])
+
+
+def _wideband_epochs(fs, n_samples, s):
+    """Code phase [chips] of every sample and the first / last code epoch of the span."""
+    t = np.arange(n_samples, dtype=np.float64) / fs
+    # the code rate follows the carrier Doppler (1 + f_d / f_carrier)
+    cp = t * 1.023e7 * (1.0 + s.doppler_hz / WIDEBAND_HZ) - s.code_delay_chips
+    return cp, int(np.floor(cp[0] / 10230.0)), int(np.floor(cp[-1] / 10230.0))
+
+
+def wideband_bit_signs(fs, n_samples, sat, periods_per_bit, epochs):
+    """The data-bit sign e5a_iq (periods_per_bit 20) / l5_iq (10) put on the code
+    epochs `epochs` (epoch 0 starts at the satellite's code delay) of an n_samples span."""
+    _, e0, e1 = _wideband_epochs(fs, n_samples, sat)
+    b0, b1 = e0 // periods_per_bit, e1 // periods_per_bit
+    nb = b1 - b0 + 2
+    return sat.data_bits(nb)[(np.asarray(epochs, np.int64) // periods_per_bit - b0) % nb]
+
+
+def _wideband_iq(fs, n_samples, sats, sec_i, sec_q_of, periods_per_bit, seed, noise, dtype):
+    rng = np.random.default_rng(seed)
+    t = np.arange(n_samples, dtype=np.float64) / fs
+    out = np.zeros(n_samples, np.complex128)
+    si = _sec_signs(sec_i)
+    for s in sats:
+        sq = _sec_signs(sec_q_of(s))
+        amp = np.sqrt(10.0 ** (s.cn0_dbhz / 10.0) / fs)
+        cp, _, _ = _wideband_epochs(fs, n_samples, s)
+        chip = np.floor(cp).astype(np.int64)
+        epoch = np.floor_divide(chip, 10230)
+        d = wideband_bit_signs(fs, n_samples, s, periods_per_bit, epoch)
+        i = s.code_i[chip % 10230] * si[epoch % len(si)] * d
+        q = s.code_q[chip % 10230] * sq[epoch % len(sq)]
+        out += amp * (i + 1j * q) / np.sqrt(2.0) * np.exp(1j * (2 * np.pi * s.doppler_hz * t + s.phase))
+    if noise:
+        out += (rng.standard_normal(n_samples) + 1j * rng.standard_normal(n_samples)) * np.sqrt(0.5)
+    return out.astype(dtype)
+
+
+def e5a_iq(fs, n_samples, sats, seed_offset=0, noise=True, dtype=np.complex64):
+    """Galileo E5a: (E5a-I x 20-chip secondary x 50 symbols/s data + j E5a-Q x the
+    PRN's 100-chip secondary) / sqrt(2); sats are WidebandSatellite objects.  The
+    first data symbol of a satellite starts with secondary chip 0 at its code delay."""
+    return _wideband_iq(fs, n_samples, sats, GAL_E5A_I_SECONDARY, lambda s: s.sec_q, 20, SEED + 4000 + seed_offset, noise,
+                        dtype)
+
+
+def l5_iq(fs, n_samples, sats, seed_offset=0, noise=True, dtype=np.complex64):
+    """GPS L5: (L5-I x 10-chip NH x 100 symbols/s data + j L5-Q x 20-chip NH) / sqrt(2)."""
+    return _wideband_iq(fs, n_samples, sats, GPS_L5I_NH, lambda s: GPS_L5Q_NH, 10, SEED + 5000 + seed_offset, noise, dtype)

@@ -74,10 +74,27 @@ void dll_pll_veml_tracking_mi355x::msg_handler_telemetry_to_trk(int tlm_event)
 // The tracking replica of start_tracking (:661-700): GPS gps_l1_ca_code_gen_float,
 // Galileo E1 galileo_e1_code_gen_sinboc11_float of E1-C when tracking the pilot
 // (E1-B as the data-component replica) or of the channel's signal, BeiDou
-// beidou_b1i_code_gen_float.
+// beidou_b1i_code_gen_float, Galileo E5a the I / Q chips of the user's code table (:696-719).
+void galileo_e5a_set_tracking_codes(gsdr_trk* engine, int slot, uint32_t prn, bool track_pilot, std::vector<float>& code)
+{
+    std::vector<float> data;
+    if (!galileo_e5a_tracking_codes(static_cast<int32_t>(prn), track_pilot, code, data))
+        throw std::runtime_error("Galileo E5a tracking: no primary code for PRN " + std::to_string(prn) +
+                                 " (code table loaded: " + (galileo_e5a_code_table_loaded() ? "yes" : "no") + ")");
+    if (!track_pilot) return;
+    const std::string secondary = galileo_e5a_q_secondary_code(static_cast<int32_t>(prn));
+    if (secondary.empty())
+        throw std::runtime_error("Galileo E5a tracking: no E5a-Q secondary code for PRN " + std::to_string(prn));
+    if (gsdr_trk_set_data_code(engine, slot, data.data(), static_cast<int>(data.size())) != GSDR_OK ||
+        gsdr_trk_set_secondary_code(engine, slot, secondary.data(), static_cast<int>(secondary.size())) != GSDR_OK)
+        throw std::runtime_error(std::string("Galileo E5a tracking: ") + gsdr_last_error());
+}
+
 void dll_pll_veml_tracking_mi355x::load_codes(uint32_t prn, std::vector<float>& code)
 {
-    if (d_signal == GSDR_SIGNAL_GAL_1B)
+    if (d_signal == GSDR_SIGNAL_GAL_5X)
+        galileo_e5a_set_tracking_codes(d_engine, 0, prn, d_conf.track_pilot, code);
+    else if (d_signal == GSDR_SIGNAL_GAL_1B)
         {
             const char sig[3] = {d_acquisition_gnss_synchro->Signal[0], d_acquisition_gnss_synchro->Signal[1], '\0'};
             if (d_conf.track_pilot)
@@ -110,13 +127,24 @@ int dll_pll_veml_tracking_mi355x::work(const void* in, int ninput_items, uint64_
             {
                 // pull-in (:1813-1844): align to the next code start after nitems_read
                 std::vector<float> code;
-                load_codes(d_acquisition_gnss_synchro->PRN, code);
                 uint64_t first = 0;
-                if (gsdr_trk_start(d_engine, 0, d_acquisition_gnss_synchro->PRN, code.data(), static_cast<int>(code.size()),
+                bool loaded = true;
+                try
+                    {
+                        load_codes(d_acquisition_gnss_synchro->PRN, code);
+                    }
+                catch (const std::runtime_error& e)
+                    {
+                        if (d_signal != GSDR_SIGNAL_GAL_5X) throw;
+                        // a PRN the user's tables lack: the channel cannot track it
+                        std::cerr << "dll_pll_veml_tracking_mi355x: " << e.what() << '\n';
+                        loaded = false;
+                    }
+                if (!loaded || gsdr_trk_start(d_engine, 0, d_acquisition_gnss_synchro->PRN, code.data(), static_cast<int>(code.size()),
                         d_acquisition_gnss_synchro->Acq_delay_samples, d_acquisition_gnss_synchro->Acq_doppler_hz,
                         d_acquisition_gnss_synchro->Acq_samplestamp_samples, nitems_read, &first) != GSDR_OK)
                     {
-                        std::cerr << "dll_pll_veml_tracking_mi355x: " << gsdr_last_error() << '\n';
+                        if (loaded) std::cerr << "dll_pll_veml_tracking_mi355x: " << gsdr_last_error() << '\n';
                         d_state = 0;
                         if (d_events) d_events(3);
                         return 0;

@@ -71,4 +71,10 @@ private:
     bool d_fault_pending{false};  // telemetry fault between start_tracking and the pull-in
 };
 
+// The "5X" replicas of start_tracking (dll_pll_veml_tracking.cc:696-719) handed to channel `slot`
+// of an engine handle: the tracking code into `code`, and for pilot tracking the data code and
+// the PRN's E5a-Q secondary code into the engine.  Throws std::runtime_error where a table lacks
+// the PRN or the engine refuses.  Shared by the per-channel block and the two pools.
+void galileo_e5a_set_tracking_codes(gsdr_trk* engine, int slot, uint32_t prn, bool track_pilot, std::vector<float>& code);
+
 #endif

@@ -7,6 +7,7 @@
 #include <stdexcept>
 #include <tuple>
 
+#include "dll_pll_veml_tracking_mi355x.h"
 #include "gnss_replicas.h"
 
 namespace
@@ -106,7 +107,9 @@ uint64_t SharedTrackingPool::start(int slot, uint32_t prn, const char signal[2],
     std::lock_guard<std::mutex> lk(d_mu);
     // the tracking replica of start_tracking (:661-700), as dll_pll_veml_tracking_mi355x
     std::vector<float> code;
-    if (d_signal == GSDR_SIGNAL_GAL_1B)
+    if (d_signal == GSDR_SIGNAL_GAL_5X)
+        galileo_e5a_set_tracking_codes(d_engine, slot, prn, d_conf.track_pilot, code);
+    else if (d_signal == GSDR_SIGNAL_GAL_1B)
         {
             const char sig[3] = {signal[0], signal[1], '\0'};
             code = galileo_e1_code_gen_sinboc11_float(d_conf.track_pilot ? "1C" : sig, prn);

@@ -73,6 +73,8 @@ std::unique_ptr<TrackingInterface> GetTrkBlock(const ConfigurationInterface* con
         return std::make_unique<GpsL1CaDllPllTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     if (implementation == "Galileo_E1_DLL_PLL_VEML_Tracking_MI355X")
         return std::make_unique<GalileoE1DllPllVemlTrackingMI355X>(configuration, role, in_streams, out_streams, device);
+    if (implementation == "Galileo_E5a_DLL_PLL_Tracking_MI355X")
+        return std::make_unique<GalileoE5aDllPllTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     if (implementation == "BEIDOU_B1I_DLL_PLL_Tracking_MI355X")
         return std::make_unique<BeidouB1iDllPllTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     return nullptr;

@@ -306,6 +306,64 @@ bool galileo_e5_a_code_gen_complex_sampled(std::vector<std::complex<float>>& des
     return true;
 }
 
+namespace
+{
+std::vector<uint8_t>& e5a_secondary_table()
+{
+    static std::vector<uint8_t> table;
+    return table;
+}
+}  // namespace
+
+bool galileo_e5a_load_secondary_table(const std::string& path, std::string* error)
+{
+    const auto refuse = [&](const std::string& why) {
+        if (error) *error = "Galileo E5a-Q secondary code table '" + path + "': " + why;
+        return false;
+    };
+    if (path.empty()) return refuse("no file named");
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) return refuse("cannot be read");
+    const auto size = static_cast<long long>(f.tellg());
+    if (size != static_cast<long long>(kGalileoE5aSecondaryTableBytes))
+        return refuse("has " + std::to_string(size) + " bytes, a table has " + std::to_string(kGalileoE5aSecondaryTableBytes) +
+                      " (50 rows of 100 bits, each padded to 13 bytes)");
+    std::vector<uint8_t> t(kGalileoE5aSecondaryTableBytes);
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(t.data()), static_cast<std::streamsize>(t.size()));
+    if (!f) return refuse("cannot be read");
+    e5a_secondary_table() = std::move(t);
+    return true;
+}
+
+bool galileo_e5a_secondary_table_loaded() { return !e5a_secondary_table().empty(); }
+
+std::string galileo_e5a_q_secondary_code(int32_t prn)
+{
+    const auto& t = e5a_secondary_table();
+    if (t.empty() || prn < 1 || prn > 50) return {};
+    const uint8_t* row = t.data() + static_cast<size_t>(prn - 1) * kGalileoE5aSecondaryRowBytes;
+    std::string s(kGalileoE5aQSecondaryLength, '0');
+    for (uint32_t i = 0; i < kGalileoE5aQSecondaryLength; i++)
+        if ((row[i >> 3] >> (7 - (i & 7))) & 1U) s[i] = '1';
+    return s;
+}
+
+bool galileo_e5a_tracking_codes(int32_t prn, bool track_pilot, std::vector<float>& code, std::vector<float>& data_code)
+{
+    const auto aux = galileo_e5_a_code_gen_complex_primary(prn, "5X");
+    if (aux.empty()) return false;
+    code.resize(aux.size());
+    data_code.clear();
+    if (track_pilot) data_code.resize(aux.size());
+    for (size_t i = 0; i < aux.size(); i++)
+        {
+            code[i] = track_pilot ? aux[i].imag() : aux[i].real();
+            if (track_pilot) data_code[i] = aux[i].real();
+        }
+    return true;
+}
+
 // ======================================================================= BeiDou B1I
 std::vector<int32_t> beidou_b1i_code_gen_int(int32_t prn, uint32_t chip_shift)
 {

@@ -60,6 +60,23 @@ std::vector<std::complex<float>> galileo_e5_a_code_gen_complex_primary(int32_t p
 bool galileo_e5_a_code_gen_complex_sampled(std::vector<std::complex<float>>& dest, uint32_t prn, const char* signal,
     int32_t sampling_freq, uint32_t chip_shift = 0);
 
+// The E5a-Q secondary codes (Galileo OS SIS ICD: one 100-chip code per PRN, the reference's
+// GALILEO_E5A_Q_SECONDARY_CODE, Galileo_E5a.h:3585) are user data as well, needed by pilot
+// tracking alone: 50 rows of 100 bits, PRN 1-50, each row MSB first and padded to
+// kGalileoE5aSecondaryRowBytes bytes; a set bit is the character '1'.  Same conventions and
+// refusals as the primary table.
+constexpr uint32_t kGalileoE5aQSecondaryLength = 100;
+constexpr uint32_t kGalileoE5aSecondaryRowBytes = 13;
+constexpr size_t kGalileoE5aSecondaryTableBytes = 50 * static_cast<size_t>(kGalileoE5aSecondaryRowBytes);
+bool galileo_e5a_load_secondary_table(const std::string& path, std::string* error = nullptr);
+bool galileo_e5a_secondary_table_loaded();
+// the PRN's E5a-Q secondary code as 100 characters '0' / '1'; empty on a bad PRN or without a table
+std::string galileo_e5a_q_secondary_code(int32_t prn);
+// The replicas of start_tracking for "5X" (dll_pll_veml_tracking.cc:696-719): pilot tracking
+// takes the E5a-Q chips as tracking code and the E5a-I chips as data code, data tracking the
+// E5a-I chips alone.  False where the primary code is missing.
+bool galileo_e5a_tracking_codes(int32_t prn, bool track_pilot, std::vector<float>& code, std::vector<float>& data_code);
+
 // ---- BeiDou B1I ----
 // beidou_b1i_code_gen_int (:26-106): +1 / -1 chips of PRN 1-63 (2046 chips; empty on a bad PRN)
 std::vector<int32_t> beidou_b1i_code_gen_int(int32_t prn, uint32_t chip_shift = 0);

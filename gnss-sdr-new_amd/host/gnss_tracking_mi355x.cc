@@ -1,7 +1,11 @@
 #include "gnss_tracking_mi355x.h"
 
 #include <cmath>
+#include <cstdlib>
 #include <iostream>
+#include <stdexcept>
+
+#include "gnss_replicas.h"
 
 namespace
 {
@@ -11,6 +15,9 @@ constexpr double GALILEO_E1_CODE_CHIP_RATE_CPS = 1.023e6;  // Galileo_E1.h
 constexpr double GALILEO_E1_B_CODE_LENGTH_CHIPS = 4092.0;
 constexpr double BEIDOU_B1I_CODE_RATE_CPS = 2.046e6;  // Beidou_B1I.h
 constexpr double BEIDOU_B1I_CODE_LENGTH_CHIPS = 2046.0;
+constexpr double GALILEO_E5A_CODE_CHIP_RATE_CPS = 1.023e7;  // Galileo_E5a.h
+constexpr double GALILEO_E5A_CODE_LENGTH_CHIPS = 10230.0;
+constexpr int GALILEO_E5A_I_SECONDARY_CODE_LENGTH = 20;
 }  // namespace
 
 void DllPllTrackingAdapterMI355X::make_block(const ConfigurationInterface* configuration, int32_t signal, int device)
@@ -85,6 +92,55 @@ GalileoE1DllPllVemlTrackingMI355X::GalileoE1DllPllVemlTrackingMI355X(const Confi
     trk_params_.signal[0] = '1';
     trk_params_.signal[1] = 'B';
     make_block(configuration, GSDR_SIGNAL_GAL_1B, device);
+}
+
+// galileo_e5a_dll_pll_tracking.cc:33-82
+GalileoE5aDllPllTrackingMI355X::GalileoE5aDllPllTrackingMI355X(const ConfigurationInterface* configuration,
+    const std::string& role, unsigned int in_streams, unsigned int out_streams, int device)
+    : DllPllTrackingAdapterMI355X(role, "Galileo_E5a_DLL_PLL_Tracking_MI355X")
+{
+    (void)in_streams;
+    (void)out_streams;
+    trk_params_.SetFromConfiguration(configuration, role);
+    trk_params_.vector_length = static_cast<uint32_t>(
+        std::round(trk_params_.fs_in / (GALILEO_E5A_CODE_CHIP_RATE_CPS / GALILEO_E5A_CODE_LENGTH_CHIPS)));
+    if (trk_params_.extend_correlation_symbols < 1)
+        {
+            trk_params_.extend_correlation_symbols = 1;
+            std::cout << "WARNING: Galileo E5a. extend_correlation_symbols must be bigger than 0. Coherent integration "
+                         "has been set to 1 symbol (1 ms)\n";
+        }
+    else if (!trk_params_.track_pilot && trk_params_.extend_correlation_symbols > GALILEO_E5A_I_SECONDARY_CODE_LENGTH)
+        {
+            trk_params_.extend_correlation_symbols = GALILEO_E5A_I_SECONDARY_CODE_LENGTH;
+            std::cout << "WARNING: Galileo E5a. extend_correlation_symbols must be lower than 21 when tracking the data "
+                         "component. Coherent integration has been set to 20 symbols (20 ms)\n";
+        }
+    if (trk_params_.extend_correlation_symbols > 1 &&
+        (trk_params_.pll_bw_narrow_hz > trk_params_.pll_bw_hz || trk_params_.dll_bw_narrow_hz > trk_params_.dll_bw_hz))
+        std::cout << "WARNING: Galileo E5a. PLL or DLL narrow tracking bandwidth is higher than wide tracking one\n";
+    trk_params_.system = 'E';
+    trk_params_.signal[0] = '5';
+    trk_params_.signal[1] = 'X';
+    // the user's code files (the repository ships none)
+    std::string why;
+    const char* env = std::getenv("GSDR_GALILEO_E5A_CODES");
+    const std::string codes = configuration->property(role + ".e5a_code_table", std::string(env ? env : ""));
+    if (codes.empty())
+        throw std::invalid_argument(role + ": the Galileo E5a primary codes are not shipped: name a code table with " + role +
+                                    ".e5a_code_table or GSDR_GALILEO_E5A_CODES (layout: gnss_replicas.h)");
+    if (!galileo_e5a_load_code_table(codes, &why)) throw std::invalid_argument(role + ": " + why);
+    if (trk_params_.track_pilot)
+        {
+            env = std::getenv("GSDR_GALILEO_E5A_SECONDARY_CODES");
+            const std::string sec = configuration->property(role + ".e5a_secondary_code_table", std::string(env ? env : ""));
+            if (sec.empty())
+                throw std::invalid_argument(role + ": pilot tracking needs the E5a-Q secondary codes, which are not shipped: "
+                                                   "name a table with " + role + ".e5a_secondary_code_table or "
+                                                   "GSDR_GALILEO_E5A_SECONDARY_CODES (layout: gnss_replicas.h)");
+            if (!galileo_e5a_load_secondary_table(sec, &why)) throw std::invalid_argument(role + ": " + why);
+        }
+    make_block(configuration, GSDR_SIGNAL_GAL_5X, device);
 }
 
 // beidou_b1i_dll_pll_tracking.cc:34-90

@@ -74,6 +74,18 @@ public:
         unsigned int in_streams, unsigned int out_streams, int device = 0);
 };
 
+// GalileoE5aDllPllTracking (galileo_e5a_dll_pll_tracking.cc:33-82), Tracking_5X.implementation =
+// Galileo_E5a_DLL_PLL_Tracking_MI355X.  The E5a codes are user files: the primary code table the
+// E5a acquisition block reads (<role>.e5a_code_table or GSDR_GALILEO_E5A_CODES) and, for pilot
+// tracking only, the E5a-Q secondary codes (<role>.e5a_secondary_code_table or
+// GSDR_GALILEO_E5A_SECONDARY_CODES; layouts: gnss_replicas.h).
+class GalileoE5aDllPllTrackingMI355X : public DllPllTrackingAdapterMI355X
+{
+public:
+    GalileoE5aDllPllTrackingMI355X(const ConfigurationInterface* configuration, const std::string& role,
+        unsigned int in_streams, unsigned int out_streams, int device = 0);
+};
+
 class BeidouB1iDllPllTrackingMI355X : public DllPllTrackingAdapterMI355X
 {
 public:

@@ -1,0 +1,146 @@
+// Self-test driver of the Galileo E5a tracking adapter (tests/test_gpu_trk_wideband.py).
+//
+//   e5a_tracking_selftest <file.conf> <iq.dat> <role> <prn> <acq delay samples> <acq doppler hz>
+//
+// Reads a GNSS-SDR style .conf (name=value lines, ';' comments), builds the block of <role>
+// (Tracking_5X) from it through the block factory -- which reads the two E5a code files the
+// .conf or the environment names -- starts it as the channel would after an acquisition at
+// stamp 0 and feeds it the gr_complex samples of iq.dat through work() in scheduler-sized
+// chunks (per-channel or pooled block, as <role>.mi355x_pool says).  Prints one JSON line:
+// whether the block was built (with the refusal's text if not), and for every Gnss_Synchro
+// it emitted the sample counter, Prompt_I, Prompt_Q, correlation_length_ms and the flags;
+// beside them, per engine record that carried a valid output, the record's own prompt pair.
+#include <algorithm>
+#include <complex>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "configuration.h"
+#include "gnss_block_factory_mi355x.h"
+#include "gnss_tracking_mi355x.h"
+#include "gsdr.h"
+
+namespace
+{
+std::string trim(const std::string& s)
+{
+    const auto a = s.find_first_not_of(" \t\r\n");
+    if (a == std::string::npos) return "";
+    return s.substr(a, s.find_last_not_of(" \t\r\n") - a + 1);
+}
+
+bool read_conf(const std::string& path, InMemoryConfiguration& config)
+{
+    std::ifstream f(path);
+    if (!f) return false;
+    std::string line;
+    while (std::getline(f, line))
+        {
+            line = trim(line.substr(0, line.find(';')));
+            const auto eq = line.find('=');
+            if (line.empty() || line[0] == '[' || eq == std::string::npos) continue;
+            config.set_property(trim(line.substr(0, eq)), trim(line.substr(eq + 1)));
+        }
+    return true;
+}
+}  // namespace
+
+int main(int argc, char** argv)
+{
+    if (argc < 7)
+        {
+            std::cerr << "usage: e5a_tracking_selftest <file.conf> <iq.dat> <role> <prn> <acq delay samples> <acq doppler hz>\n";
+            return 2;
+        }
+    InMemoryConfiguration config;
+    if (!read_conf(argv[1], config))
+        {
+            std::cerr << "cannot read " << argv[1] << '\n';
+            return 2;
+        }
+    std::ifstream f(argv[2], std::ios::binary | std::ios::ate);
+    if (!f)
+        {
+            std::cerr << "cannot read " << argv[2] << '\n';
+            return 2;
+        }
+    std::vector<std::complex<float>> x(static_cast<size_t>(f.tellg()) / sizeof(std::complex<float>));
+    f.seekg(0);
+    f.read(reinterpret_cast<char*>(x.data()), static_cast<std::streamsize>(x.size() * sizeof(std::complex<float>)));
+    const std::string role = argv[3];
+
+    std::unique_ptr<TrackingInterface> trk;
+    try
+        {
+            trk = gsdr_factory::GetTrkBlock(&config, role, 1, 1, 0);
+        }
+    catch (const std::exception& e)
+        {
+            std::string what = e.what();
+            std::replace(what.begin(), what.end(), '"', '\'');
+            std::cout << "{\"built\": false, \"error\": \"" << what << "\"}\n";
+            return 1;
+        }
+    auto* adapter = dynamic_cast<GalileoE5aDllPllTrackingMI355X*>(trk.get());
+    if (!adapter)
+        {
+            std::cout << "{\"built\": false, \"error\": \"not the Galileo E5a tracking adapter\"}\n";
+            return 1;
+        }
+    Gnss_Synchro gs;
+    gs.System = 'E';
+    gs.Signal[0] = '5';
+    gs.Signal[1] = 'X';
+    gs.PRN = static_cast<uint32_t>(std::atoi(argv[4]));
+    gs.Acq_delay_samples = std::atof(argv[5]);
+    gs.Acq_doppler_hz = std::atof(argv[6]);
+    gs.Acq_samplestamp_samples = 0;
+    trk->set_channel(0);
+    trk->set_gnss_synchro(&gs);
+    trk->start_tracking();
+    auto* blk = adapter->get_block();
+    std::vector<gsdr_trk_epoch> valid;
+    blk->set_record_sink([&valid](const gsdr_trk_epoch& e) {
+        if (e.flags & GSDR_TRK_F_VALID_OUTPUT) valid.push_back(e);
+    });
+    std::vector<Gnss_Synchro> outs;
+    uint64_t nread = 0;
+    for (;;)
+        {
+            if (nread + static_cast<uint64_t>(blk->forecast()) > x.size()) break;
+            const int avail = static_cast<int>(std::min<uint64_t>(16384, x.size() - nread));
+            Gnss_Synchro out{};
+            int nout = 0;
+            const int used = blk->work(x.data() + nread, avail, nread, &out, &nout);
+            if (nout == 1) outs.push_back(out);
+            if (used <= 0 && nout == 0) break;
+            nread += static_cast<uint64_t>(std::max(used, 0));
+        }
+    blk->flush();
+    for (int guard = 0; guard < 100000; ++guard)
+        {
+            Gnss_Synchro out{};
+            int nout = 0;
+            blk->work(nullptr, 0, nread, &out, &nout);
+            if (nout == 0) break;
+            outs.push_back(out);
+        }
+    std::printf("{\"built\": true, \"pooled\": %s, \"vector_length\": %u, \"outputs\": [", adapter->pooled() ? "true" : "false",
+        adapter->conf().vector_length);
+    for (size_t i = 0; i < outs.size(); ++i)
+        std::printf("%s[%llu, %.17g, %.17g, %d, %d, %d]", i ? ", " : "", static_cast<unsigned long long>(outs[i].Tracking_sample_counter),
+            outs[i].Prompt_I, outs[i].Prompt_Q, outs[i].correlation_length_ms, outs[i].Flag_valid_symbol_output ? 1 : 0,
+            outs[i].Flag_PLL_180_deg_phase_locked ? 1 : 0);
+    std::printf("], \"records\": [");
+    for (size_t i = 0; i < valid.size(); ++i)
+        std::printf("%s[%llu, %.17g, %.17g, %.9g, %.9g]", i ? ", " : "", static_cast<unsigned long long>(valid[i].sample_counter),
+            valid[i].prompt_i, valid[i].prompt_q, valid[i].data_prompt[0], valid[i].data_prompt[1]);
+    std::printf("]}\n");
+    return 0;
+}

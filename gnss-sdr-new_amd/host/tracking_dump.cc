@@ -77,6 +77,11 @@ double TrackingDump::pull_in_code_phase(int32_t signal, double fs_in, uint64_t n
             rate = 2.046e6;
             length = 2046.0;
         }
+    if (signal == GSDR_SIGNAL_GAL_5X || signal == GSDR_SIGNAL_GPS_L5)
+        {
+            rate = 1.023e7;
+            length = 10230.0;
+        }
     const int64_t diff = static_cast<int64_t>(nitems_read) - static_cast<int64_t>(acq_sample_stamp);
     const double delta = static_cast<double>(diff) - acq_delay_samples;
     const double t_prn_samples = 1.0 / rate * length * fs_in;

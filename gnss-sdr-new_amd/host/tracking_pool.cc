@@ -3,6 +3,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "dll_pll_veml_tracking_mi355x.h"
 #include "gnss_replicas.h"
 
 TrackingPool::TrackingPool(const Dll_Pll_Conf& conf, int32_t signal, uint32_t max_channels, gsdr_stream* ring, int device)
@@ -22,7 +23,9 @@ void TrackingPool::start(uint32_t slot, Gnss_Synchro* gs, uint64_t nitems_read)
 {
     if (slot >= d_max || !gs) throw std::invalid_argument("TrackingPool::start: bad slot or Gnss_Synchro");
     std::vector<float> code;
-    if (d_signal == GSDR_SIGNAL_GAL_1B)
+    if (d_signal == GSDR_SIGNAL_GAL_5X)
+        galileo_e5a_set_tracking_codes(d_engine, static_cast<int>(slot), gs->PRN, d_conf.track_pilot, code);
+    else if (d_signal == GSDR_SIGNAL_GAL_1B)
         {
             const char sig[3] = {gs->Signal[0], gs->Signal[1], '\0'};
             code = galileo_e1_code_gen_sinboc11_float(d_conf.track_pilot ? "1C" : sig, gs->PRN);

@@ -853,6 +853,10 @@ typedef struct gsdr_trk gsdr_trk;
 #define GSDR_SIGNAL_GPS_1C 0 /* GPS L1 C/A (dll_pll_veml_tracking.cc:170-191) */
 #define GSDR_SIGNAL_GAL_1B 1 /* Galileo E1 OS, VEML 5 taps, pilot (E1C) or data (E1B) tracking (:258-290) */
 #define GSDR_SIGNAL_BDS_B1 2 /* BeiDou B1I D1 (NH secondary code) / D2 GEO (preamble) (:391-411, :762-795) */
+#define GSDR_SIGNAL_GAL_5X 3 /* Galileo E5a, E/P/L, pilot (E5a-Q, per-PRN 100-chip secondary code) or data
+                                (E5a-I, 20-chip secondary code) tracking (:289-319, :696-719) */
+#define GSDR_SIGNAL_GPS_L5 4 /* GPS L5, E/P/L, pilot (L5-Q, 20-chip NH code) or data (L5-I, 10-chip NH code)
+                                tracking (:210-244, :667-680) */
 
 /* Mirrors Dll_Pll_Conf (src/algorithms/tracking/libs/dll_pll_conf.h:30-84);
  * gsdr_trk_conf_default() fills the reference defaults (incl. the gflags
@@ -894,6 +898,7 @@ typedef struct gsdr_trk_conf
     int32_t high_dyn;    /* Dll_Pll_Conf::high_dyn: high-dynamics resampler/rotator + carrier/code rate
                             estimates from the step histories (dll_pll_veml_tracking.cc:1232-1284) */
     int32_t track_pilot; /* Dll_Pll_Conf::track_pilot (default 1); forced 0 for GPS L1 C/A and BeiDou B1I */
+                         /* (:183, :402); Galileo E1, Galileo E5a and GPS L5 honour it */
     uint32_t smoother_length; /* Dll_Pll_Conf::smoother_length (default 10, at most 32): histories of 2x that */
 } gsdr_trk_conf;
 
@@ -914,8 +919,8 @@ typedef struct gsdr_trk_epoch
     double acc_carrier_phase_rad;  /* Carrier_phase_rads */
     double cn0_db_hz;              /* CN0_dB_hz */
     double carrier_lock_test;
-    double prompt_i;               /* Prompt_I (valid output only) */
-    double prompt_q;               /* Prompt_Q (valid output only) */
+    double prompt_i;               /* Prompt_I (valid output only); with d_interchange_iq (E5a pilot, L5 data: */
+    double prompt_q;               /* Prompt_Q  :242, :310) imag / real of d_P_data_accu (:2001-2010, :2054-2063) */
     double evm;                    /* EVM (fork indicator, :1027-1053) */
     float data_prompt[2];          /* pilot tracking: the data-component prompt of the call (d_Prompt_Data[0]) */
     float carrier_rate;            /* high_dyn: (float)d_carrier_phase_rate_step_rad after the call [rad/sample^2] */
@@ -956,6 +961,12 @@ int gsdr_trk_start(gsdr_trk* trk, int ch, uint32_t prn, const float* code, int c
  * dll_pll_veml_tracking.cc:681-689, e.g. galileo_e1_code_gen_sinboc11_float of
  * E1B), code_samples floats.  Call before gsdr_trk_start for that channel. */
 int gsdr_trk_set_data_code(gsdr_trk* trk, int ch, const float* data_code, int code_samples);
+/* Galileo E5a pilot tracking: the PRN's E5a-Q secondary code for channel ch
+ * (d_secondary_code_string = GALILEO_E5A_Q_SECONDARY_CODE[PRN - 1],
+ * dll_pll_veml_tracking.cc:703), len characters '0' / '1', 1 <= len <= 160.  Required
+ * before gsdr_trk_start on such a handle (GSDR_E_STATE otherwise); handles of every
+ * other signal and mode refuse it with GSDR_E_STATE.  The library ships no E5a table. */
+int gsdr_trk_set_secondary_code(gsdr_trk* trk, int ch, const char* bits, int len);
 /* stop_tracking: channel to state 0 (standby). */
 int gsdr_trk_stop(gsdr_trk* trk, int ch);
 /* msg_handler_telemetry_to_trk with tlm_event 1 (dll_pll_veml_tracking.cc:614-637,
