@@ -6,7 +6,6 @@
 #include <stdexcept>
 
 #include "gnss_replicas.h"
-#include "gnss_sdr_flags.h"
 
 namespace
 {
@@ -18,18 +17,8 @@ constexpr double GALILEO_E1_B_CODE_LENGTH_CHIPS = 4092.0;
 // galileo_e1_pcps_8ms_ambiguous_acquisition.cc:35-118: the same text but for the code buffers
 GalileoE1PairAcquisitionMI355X::GalileoE1PairAcquisitionMI355X(const ConfigurationInterface* configuration,
     const std::string& role, unsigned int in_streams, unsigned int out_streams, int device, Pair_Acq_Conf::Policy policy)
-    : configuration_(configuration), role_(role)
+    : AcquisitionItemAdapterMI355X(configuration, role, 4000000, 4, "../data/acquisition.dat")
 {
-    const std::string default_item_type("gr_complex");
-    const std::string default_dump_filename("../data/acquisition.dat");
-
-    item_type_ = configuration_->property(role + ".item_type", default_item_type);
-    const int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(4000000));
-    fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
-    dump_ = configuration_->property(role + ".dump", false);
-    doppler_max_ = static_cast<unsigned int>(configuration_->property(role + ".doppler_max", 5000));
-    if (FLAGS_doppler_max != 0) doppler_max_ = static_cast<unsigned int>(FLAGS_doppler_max);
-    sampled_ms_ = static_cast<unsigned int>(configuration_->property(role + ".coherent_integration_time_ms", 4));
     if (sampled_ms_ % 4 != 0)
         {
             sampled_ms_ = static_cast<unsigned int>(static_cast<int>(sampled_ms_ / 4) * 4);
@@ -38,7 +27,6 @@ GalileoE1PairAcquisitionMI355X::GalileoE1PairAcquisitionMI355X(const Configurati
                       << sampled_ms_ << " ms will be used.\n";
         }
     max_dwells_ = static_cast<unsigned int>(configuration_->property(role + ".max_dwells", 1));
-    dump_filename_ = configuration_->property(role + ".dump_filename", default_dump_filename);
 
     // -- Find number of samples per spreading code (4 ms)
     code_length_ = static_cast<unsigned int>(
@@ -60,37 +48,9 @@ GalileoE1PairAcquisitionMI355X::GalileoE1PairAcquisitionMI355X(const Configurati
         throw std::invalid_argument(role + ".mi355x_carrier must be exact, generic or avx2");
     conf.wipeoff_mode = carrier == "generic" ? GSDR_WIPE_GENERIC : (carrier == "avx2" ? GSDR_WIPE_AVX2 : GSDR_WIPE_EXACT);
 
-    // the reference builds the gr_complex block only; any other item type gets a warning
-    item_size_ = sizeof(std::complex<float>);
-    if (item_type_ != "gr_complex") std::cerr << item_type_ << " unknown acquisition item type\n";
+    warn_item_type();
     acquisition_ = std::make_unique<pcps_pair_acquisition_mi355x>(conf, device);
-
-    if (in_streams > 1) std::cerr << "This implementation only supports one input stream\n";
-    if (out_streams > 0) std::cerr << "This implementation does not provide an output stream\n";
-}
-
-void GalileoE1PairAcquisitionMI355X::set_doppler_max(unsigned int doppler_max)
-{
-    doppler_max_ = doppler_max;
-    acquisition_->set_doppler_max(doppler_max_);
-}
-
-void GalileoE1PairAcquisitionMI355X::set_doppler_step(unsigned int doppler_step)
-{
-    doppler_step_ = doppler_step;
-    acquisition_->set_doppler_step(doppler_step_);
-}
-
-void GalileoE1PairAcquisitionMI355X::set_gnss_synchro(Gnss_Synchro* gnss_synchro)
-{
-    gnss_synchro_ = gnss_synchro;
-    acquisition_->set_gnss_synchro(gnss_synchro_);
-}
-
-void GalileoE1PairAcquisitionMI355X::set_channel(unsigned int channel)
-{
-    channel_ = channel;
-    acquisition_->set_channel(channel_);
+    attach_block(acquisition_.get(), in_streams, out_streams);
 }
 
 // ---------------------------------------------------------------- CCCWSR
@@ -101,13 +61,6 @@ GalileoE1PcpsCccwsrAmbiguousAcquisitionMI355X::GalileoE1PcpsCccwsrAmbiguousAcqui
 {
     code_data_ = std::vector<std::complex<float>>(vector_length_);
     code_pilot_ = std::vector<std::complex<float>>(vector_length_);
-}
-
-// :115-119
-void GalileoE1PcpsCccwsrAmbiguousAcquisitionMI355X::stop_acquisition()
-{
-    acquisition_->set_state(0);
-    acquisition_->set_active(false);
 }
 
 // :122-132: the configured threshold; calculate_threshold is not implemented there
@@ -141,15 +94,6 @@ GalileoE1Pcps8msAmbiguousAcquisitionMI355X::GalileoE1Pcps8msAmbiguousAcquisition
 // :121-124
 void GalileoE1Pcps8msAmbiguousAcquisitionMI355X::stop_acquisition() { acquisition_->set_active(false); }
 
-// :127-152: per-channel pfa, then the role's; without one, the configured threshold
-void GalileoE1Pcps8msAmbiguousAcquisitionMI355X::set_threshold(float threshold)
-{
-    float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0F);
-    if (pfa == 0.0) pfa = configuration_->property(role_ + ".pfa", 0.0F);
-    threshold_ = pfa == 0.0 ? threshold : calculate_threshold(pfa);
-    acquisition_->set_threshold(threshold_);
-}
-
 // :203-226: the code of the synchro's signal, repeated sampled_ms / 4 times
 void GalileoE1Pcps8msAmbiguousAcquisitionMI355X::set_local_code()
 {
@@ -164,16 +108,5 @@ void GalileoE1Pcps8msAmbiguousAcquisitionMI355X::set_local_code()
 // :239-257: the exponential distribution's quantile with lambda = vector_length_, in double
 float GalileoE1Pcps8msAmbiguousAcquisitionMI355X::calculate_threshold(float pfa) const
 {
-    // (the reference's loop does not end with a zero step)
-    if (doppler_step_ == 0) throw std::invalid_argument(role_ + ": set_doppler_step before a pfa threshold");
-    unsigned int frequency_bins = 0;
-    for (int doppler = -static_cast<int>(doppler_max_); doppler <= static_cast<int>(doppler_max_);
-         doppler += static_cast<int>(doppler_step_))
-        frequency_bins++;
-    const unsigned int ncells = vector_length_ * frequency_bins;
-    const double exponent = 1 / static_cast<double>(ncells);
-    const double val = std::pow(1.0 - pfa, exponent);
-    const auto lambda = static_cast<double>(vector_length_);
-    // quantile(exponential_distribution(lambda), val) = -log1p(-val) / lambda
-    return static_cast<float>(-std::log1p(-val) / lambda);
+    return AcquisitionItemAdapterMI355X::calculate_threshold(pfa, vector_length_, static_cast<double>(vector_length_));
 }

@@ -1,28 +1,20 @@
 #include "galileo_e5a_noncoherent_iq_acquisition_caf_block_mi355x.h"
 
 #include <algorithm>
-#include <iostream>
 #include <stdexcept>
-#include <string>
 
 namespace
 {
-[[noreturn]] void fail()
-{
-    throw std::runtime_error(std::string("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: ") + gsdr_last_error());
-}
 constexpr uint32_t kMaxBatch = 32;
 }  // namespace
 
 // galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc:55-137
 galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::galileo_e5a_noncoherentIQ_acquisition_caf_mi355x(
     const E5a_Iq_Caf_Acq_Conf& conf, int device)
-    : d_conf(conf),
-      d_device(device),
+    : acquisition_item_block_mi355x("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x", device, conf.fs_in,
+          conf.doppler_max, conf.sampled_ms * static_cast<uint32_t>(conf.samples_per_ms)),
       d_CAF_window_hz(conf.CAF_window_hz),
-      d_doppler_max(conf.doppler_max),
       d_samples_per_code(static_cast<uint32_t>(conf.samples_per_code)),
-      d_fft_size(conf.sampled_ms * static_cast<uint32_t>(conf.samples_per_ms)),
       d_sampled_ms(conf.Zero_padding > 0 ? 1U : conf.sampled_ms),
       d_max_dwells(conf.max_dwells),
       d_batch(std::max(1U, std::min(conf.max_dwells, kMaxBatch))),
@@ -30,18 +22,14 @@ galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::galileo_e5a_noncoherentIQ_acqu
       d_both_signal_components(conf.both_signal_components),
       d_enable_monitor_output(conf.enable_monitor_output)
 {
+    d_doppler_step = 250;  // :88
     // d_well_count == d_max_dwells (:686) is never met from 1 upwards
     if (d_max_dwells < 1)
         throw std::invalid_argument("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: max_dwells must be >= 1");
-    if (d_fft_size == 0 || d_samples_per_code == 0 || d_samples_per_code > d_fft_size)
+    if (d_item_samples == 0 || d_samples_per_code == 0 || d_samples_per_code > d_item_samples)
         throw std::invalid_argument("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: empty items or code");
     if (d_sampled_ms < 1 || d_sampled_ms > 3)
         throw std::invalid_argument("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: 1 to 3 ms of coherent integration");
-}
-
-galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::~galileo_e5a_noncoherentIQ_acquisition_caf_mi355x()
-{
-    gsdr_acq_destroy(d_engine);
 }
 
 void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::upload_code()
@@ -56,60 +44,22 @@ void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::upload_code()
 // :160-208
 void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::set_local_code(std::complex<float>* codeI, std::complex<float>* codeQ)
 {
-    d_code_i.assign(codeI, codeI + d_fft_size);
-    if (d_both_signal_components) d_code_q.assign(codeQ, codeQ + d_fft_size);
+    d_code_i.assign(codeI, codeI + d_item_samples);
+    if (d_both_signal_components) d_code_q.assign(codeQ, codeQ + d_item_samples);
     upload_code();
 }
 
 // :211-255
 void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::init()
 {
-    d_gnss_synchro->Flag_valid_acquisition = false;
-    d_gnss_synchro->Flag_valid_symbol_output = false;
-    d_gnss_synchro->Flag_valid_pseudorange = false;
-    d_gnss_synchro->Flag_valid_word = false;
-    d_gnss_synchro->Acq_delay_samples = 0.0;
-    d_gnss_synchro->Acq_doppler_hz = 0.0;
-    d_gnss_synchro->Acq_doppler_step = 0U;
-    d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-    d_mag = 0.0;
-    d_input_power = 0.0;
-
+    clear_synchro();
     // the reference's loop over the bins does not end with a zero step (:227-232)
     if (d_doppler_step == 0)
         throw std::invalid_argument("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: doppler_step 0");
-
-    // Count the number of bins (:226-232)
-    d_num_doppler_bins = 0;
-    for (auto doppler = -static_cast<int32_t>(d_doppler_max); doppler <= static_cast<int32_t>(d_doppler_max);
-         doppler += static_cast<int32_t>(d_doppler_step))
-        d_num_doppler_bins++;
-
-    gsdr_acq_destroy(d_engine);
-    d_engine = nullptr;
-    const uint32_t nslots = (d_sampled_ms > 1 ? 2U : 1U) * (d_both_signal_components ? 2U : 1U);
-    gsdr_acq_conf c{};
-    c.fs_in = d_conf.fs_in;
-    c.consumed_samples = d_fft_size;
-    c.fft_size = d_fft_size;
-    c.samples_per_code = static_cast<float>(d_samples_per_code);
-    c.samples_per_chip = 1;  // the second-peak window: not used by an IQ-CAF run
-    c.doppler_max = static_cast<int32_t>(d_doppler_max);
-    c.doppler_step = d_doppler_step;
-    c.num_doppler_bins = d_num_doppler_bins;
-    c.pfa = 0.0F;
-    c.max_dwells = 1;  // every item is a grid of its own; the dwells are folded here
-    c.item_type = GSDR_ITEM_GR_COMPLEX;
-    c.max_prns = nslots;
+    gsdr_acq_conf c = grid_conf(d_item_samples, d_samples_per_code);
+    c.max_prns = (d_sampled_ms > 1 ? 2U : 1U) * (d_both_signal_components ? 2U : 1U);
     c.max_blocks = d_batch;
-    c.sampled_ms = 1;
-    c.ms_per_code = 1;
-    if (gsdr_acq_create(d_device, &c, &d_engine) != GSDR_OK)
-        {
-            d_engine = nullptr;
-            fail();
-        }
-    if (gsdr_acq_set_wipeoff(d_engine, GSDR_WIPE_EXACT) != GSDR_OK) fail();
+    create_engine(c, GSDR_WIPE_EXACT);
     // refuses the windows with which :605 divides by zero or :609-667 leave their vectors
     if (gsdr_acq_set_iq_caf(d_engine, d_samples_per_code, d_sampled_ms, d_both_signal_components ? 1 : 0,
             d_CAF_window_hz) != GSDR_OK)
@@ -119,55 +69,21 @@ void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::init()
 }
 
 // the restart of :261-271 and :310-321
-void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::restart()
-{
-    d_gnss_synchro->Acq_delay_samples = 0.0;
-    d_gnss_synchro->Acq_doppler_hz = 0.0;
-    d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-    d_gnss_synchro->Acq_doppler_step = 0U;
-    d_well_count = 0;
-    d_mag = 0.0;
-    d_input_power = 0.0;
-    d_test_statistics = 0.0;
-}
-
-// :258-279
-void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::set_state(int32_t state)
-{
-    d_state = state;
-    if (d_state == 1)
-        restart();
-    else if (d_state != 0)
-        std::cerr << "State can only be set to 0 or 1\n";
-}
-
-void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::set_ring(gsdr_stream* ring, uint64_t origin)
-{
-    d_ring = ring;
-    d_ring_origin = origin;
-}
+void galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::restart_counters() { d_well_count = 0; }
 
 // general_work (:282-764)
 int galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::work(const std::complex<float>* in, int ninput_items,
     Gnss_Synchro* monitor_out, int* noutput_items)
 {
-    int consumed = 0;
     if (noutput_items) *noutput_items = 0;
     switch (d_state)
         {
         case 0:
-            if (d_active)
-                {
-                    restart();
-                    d_state = 1;
-                }
-            d_sample_counter += static_cast<uint64_t>(d_fft_size) * static_cast<uint64_t>(ninput_items);
-            consumed = ninput_items;
-            break;
+            return idle_step(ninput_items);
         case 1:
             {
                 if (!d_engine) throw std::runtime_error("galileo_e5a_noncoherentIQ_acquisition_caf_mi355x: init() first");
-                if (ninput_items < 1) break;
+                if (ninput_items < 1) return 0;
                 // as many dwells of the reference as items offered, in one engine call: no attempt
                 // goes beyond max_dwells items
                 const uint32_t left = d_max_dwells > d_well_count ? d_max_dwells - d_well_count : 1U;
@@ -180,9 +96,8 @@ int galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::work(const std::complex<fl
                 for (uint32_t k = 0; k < n; ++k)
                     {
                         d_last = d_records[k];
-                        // the engine stamps the item's first sample; the reference has counted the
-                        // item before it runs the grid, so its stamp is the item's end (:359, :563)
-                        d_sample_counter += d_fft_size;
+                        // the reference has counted the item before it runs the grid (:359, :563)
+                        d_sample_counter += d_item_samples;
                         d_input_power = d_last.input_power;
                         d_mag = 0.0;
                         d_well_count++;
@@ -193,10 +108,7 @@ int galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::work(const std::complex<fl
                                 d_mag = d_last.mag;
                                 if (d_test_statistics < (d_mag / d_input_power) || !d_bit_transition_flag)
                                     {
-                                        d_gnss_synchro->Acq_delay_samples = d_last.acq_delay_samples;
-                                        d_gnss_synchro->Acq_doppler_hz = static_cast<double>(d_last.doppler_hz);
-                                        d_gnss_synchro->Acq_samplestamp_samples = d_last.samplestamp + d_fft_size;
-                                        d_gnss_synchro->Acq_doppler_step = d_doppler_step;
+                                        take_winner(d_last.acq_delay_samples, d_last.doppler_hz, d_last.samplestamp);
                                         d_test_statistics = d_mag / d_input_power;
                                     }
                             }
@@ -205,28 +117,13 @@ int galileo_e5a_noncoherentIQ_acquisition_caf_mi355x::work(const std::complex<fl
                     }
                 // :686-700 (n never passes the dwell that decides)
                 if (d_well_count == d_max_dwells) d_state = d_test_statistics > d_threshold ? 3 : 4;
-                consumed = static_cast<int>(n);
-                break;
+                return static_cast<int>(n);
             }
         case 3:
         case 4:
-            {
-                const int message = d_state == 3 ? 1 : 2;
-                // :728-735: the monitor output of a positive acquisition
-                if (d_state == 3 && d_enable_monitor_output && monitor_out)
-                    {
-                        *monitor_out = *d_gnss_synchro;
-                        if (noutput_items) *noutput_items = 1;
-                    }
-                d_active = false;
-                d_state = 0;
-                d_sample_counter += static_cast<uint64_t>(d_fft_size) * static_cast<uint64_t>(ninput_items);
-                consumed = ninput_items;
-                if (d_events) d_events(message);
-                break;
-            }
+            // :728-735: the monitor output of a positive acquisition
+            return terminal_step(d_state == 3, ninput_items, d_enable_monitor_output ? monitor_out : nullptr, noutput_items);
         default:
-            break;
+            return 0;
         }
-    return consumed;
 }

@@ -26,11 +26,9 @@
 
 #include <complex>
 #include <cstdint>
-#include <functional>
 #include <vector>
 
-#include "gnss_synchro.h"
-#include "gsdr.h"
+#include "acquisition_item_block_mi355x.h"
 
 // the arguments of galileo_e5a_noncoherentIQ_make_acquisition_caf_cc
 struct E5a_Iq_Caf_Acq_Conf
@@ -48,31 +46,15 @@ struct E5a_Iq_Caf_Acq_Conf
     bool enable_monitor_output{false};
 };
 
-class galileo_e5a_noncoherentIQ_acquisition_caf_mi355x
+class galileo_e5a_noncoherentIQ_acquisition_caf_mi355x : public acquisition_item_block_mi355x
 {
 public:
     explicit galileo_e5a_noncoherentIQ_acquisition_caf_mi355x(const E5a_Iq_Caf_Acq_Conf& conf, int device = 0);
-    ~galileo_e5a_noncoherentIQ_acquisition_caf_mi355x();
-    galileo_e5a_noncoherentIQ_acquisition_caf_mi355x(const galileo_e5a_noncoherentIQ_acquisition_caf_mi355x&) = delete;
-    galileo_e5a_noncoherentIQ_acquisition_caf_mi355x& operator=(const galileo_e5a_noncoherentIQ_acquisition_caf_mi355x&) =
-        delete;
 
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) { d_gnss_synchro = p_gnss_synchro; }
-    uint32_t mag() const { return static_cast<uint32_t>(d_mag); }
     // counts the Doppler bins and creates the wipe-offs (:211-255): here, the engine handle
-    void init();
+    void init() override;
     // :160-208: fft_size samples each; codeQ is read with both components only
     void set_local_code(std::complex<float>* codeI, std::complex<float>* codeQ);
-    void set_active(bool active) { d_active = active; }
-    void set_state(int32_t state);
-    void set_channel(uint32_t channel) { d_channel = channel; }
-    void set_threshold(float threshold) { d_threshold = threshold; }
-    void set_doppler_max(uint32_t doppler_max) { d_doppler_max = doppler_max; }
-    void set_doppler_step(uint32_t doppler_step) { d_doppler_step = doppler_step; }
-    void set_event_handler(std::function<void(int)> h) { d_events = std::move(h); }
-    // Ring path: the items work() is given are also samples [origin + d_sample_counter, ...)
-    // of the device ring, and state 1 reads its items there in place.
-    void set_ring(gsdr_stream* ring, uint64_t origin);
 
     // general_work: `in` holds ninput_items items of fft_size() samples; returns the items
     // consumed (consume_each).  monitor_out, when given, receives the Gnss_Synchro of a positive
@@ -80,15 +62,8 @@ public:
     int work(const std::complex<float>* in, int ninput_items, Gnss_Synchro* monitor_out = nullptr,
         int* noutput_items = nullptr);
 
-    int state() const { return d_state; }
-    uint64_t sample_counter() const { return d_sample_counter; }
-    float threshold() const { return d_threshold; }
-    float test_statistics() const { return d_test_statistics; }
-    float input_power() const { return d_input_power; }
-    float mag_value() const { return d_mag; }
     uint32_t well_count() const { return d_well_count; }
-    uint32_t num_doppler_bins() const { return d_num_doppler_bins; }
-    uint32_t fft_size() const { return d_fft_size; }
+    uint32_t fft_size() const { return d_item_samples; }
     uint32_t coherent_ms() const { return d_sampled_ms; }
     uint32_t batch_items() const { return d_batch; }
     bool both_signal_components() const { return d_both_signal_components; }
@@ -96,38 +71,19 @@ public:
 
 private:
     void upload_code();
-    void restart();
+    void restart_counters() override;
 
-    E5a_Iq_Caf_Acq_Conf d_conf;
-    int d_device;
-    gsdr_acq* d_engine{nullptr};
-    gsdr_stream* d_ring{nullptr};
-    uint64_t d_ring_origin{0};
-    Gnss_Synchro* d_gnss_synchro{nullptr};
-    std::function<void(int)> d_events;
     std::vector<std::complex<float>> d_code_i, d_code_q;
     std::vector<gsdr_acq_iq_caf_result> d_records;
     gsdr_acq_iq_caf_result d_last{};
-    uint64_t d_sample_counter{0};
-    float d_threshold{0.0F};
-    float d_mag{0.0F};
-    float d_input_power{0.0F};
-    float d_test_statistics{0.0F};
-    int32_t d_state{0};
     int32_t d_CAF_window_hz;
-    uint32_t d_channel{0};
-    uint32_t d_doppler_max;
-    uint32_t d_doppler_step{250};  // :88
     uint32_t d_samples_per_code;
-    uint32_t d_fft_size;
     uint32_t d_sampled_ms;  // 1 with Zero_padding (:104-111)
     uint32_t d_max_dwells;
     uint32_t d_well_count{0};
     uint32_t d_batch;  // items per engine call: no attempt takes more than max_dwells
-    uint32_t d_num_doppler_bins{0};
     bool d_bit_transition_flag;
     bool d_both_signal_components;
-    bool d_active{false};
     bool d_enable_monitor_output;
 };
 

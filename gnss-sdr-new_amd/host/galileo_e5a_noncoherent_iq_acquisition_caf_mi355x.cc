@@ -7,7 +7,6 @@
 #include <stdexcept>
 
 #include "gnss_replicas.h"
-#include "gnss_sdr_flags.h"
 
 namespace
 {
@@ -31,20 +30,10 @@ void GalileoE5aNoncoherentIQAcquisitionCafMI355X::load_code_table(const Configur
 GalileoE5aNoncoherentIQAcquisitionCafMI355X::GalileoE5aNoncoherentIQAcquisitionCafMI355X(
     const ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams,
     unsigned int out_streams, int device)
-    : configuration_(configuration), role_(role)
+    : AcquisitionItemAdapterMI355X(configuration, role, 32000000, 1, "../data/acquisition.dat")
 {
-    const std::string default_item_type("gr_complex");
-    const std::string default_dump_filename("../data/acquisition.dat");
-
-    item_type_ = configuration_->property(role + ".item_type", default_item_type);
-    const int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(32000000));
-    fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
-    dump_ = configuration_->property(role + ".dump", false);
-    doppler_max_ = static_cast<unsigned int>(configuration_->property(role + ".doppler_max", 5000));
-    if (FLAGS_doppler_max != 0) doppler_max_ = static_cast<unsigned int>(FLAGS_doppler_max);
     CAF_window_hz_ = configuration_->property(role + ".CAF_window_hz", 0);
     Zero_padding = configuration_->property(role + ".Zero_padding", 0);
-    sampled_ms_ = static_cast<unsigned int>(configuration_->property(role + ".coherent_integration_time_ms", 1));
     if (sampled_ms_ > 3)
         {
             sampled_ms_ = 3;
@@ -56,7 +45,6 @@ GalileoE5aNoncoherentIQAcquisitionCafMI355X::GalileoE5aNoncoherentIQAcquisitionC
             std::cout << "Zero padding activated. Changing to 1ms code + 1ms zero padding\n";
         }
     max_dwells_ = static_cast<unsigned int>(configuration_->property(role + ".max_dwells", 1));
-    dump_filename_ = configuration_->property(role + ".dump_filename", default_dump_filename);
     bit_transition_flag_ = configuration_->property(role + ".bit_transition_flag", false);
 
     // samples per spreading code (1 ms)
@@ -82,51 +70,10 @@ GalileoE5aNoncoherentIQAcquisitionCafMI355X::GalileoE5aNoncoherentIQAcquisitionC
     conf.CAF_window_hz = CAF_window_hz_;
     conf.Zero_padding = Zero_padding;
     conf.enable_monitor_output = enable_monitor_output;
-    // the reference builds the gr_complex block only; any other item type gets a warning
-    if (item_type_ != "gr_complex") std::cerr << item_type_ << " unknown acquisition item type\n";
+
+    warn_item_type();
     acquisition_ = std::make_unique<galileo_e5a_noncoherentIQ_acquisition_caf_mi355x>(conf, device);
-
-    if (in_streams > 1) std::cerr << "This implementation only supports one input stream\n";
-    if (out_streams > 0) std::cerr << "This implementation does not provide an output stream\n";
-}
-
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::stop_acquisition()
-{
-    acquisition_->set_state(0);
-    acquisition_->set_active(false);
-}
-
-// per-channel pfa, then the role's; without one, the configured threshold (:137-161)
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_threshold(float threshold)
-{
-    float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0F);
-    if (pfa == 0.0) pfa = configuration_->property(role_ + ".pfa", 0.0F);
-    threshold_ = pfa == 0.0 ? threshold : calculate_threshold(pfa);
-    acquisition_->set_threshold(threshold_);
-}
-
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_doppler_max(unsigned int doppler_max)
-{
-    doppler_max_ = doppler_max;
-    acquisition_->set_doppler_max(doppler_max_);
-}
-
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_doppler_step(unsigned int doppler_step)
-{
-    doppler_step_ = doppler_step;
-    acquisition_->set_doppler_step(doppler_step_);
-}
-
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_gnss_synchro(Gnss_Synchro* gnss_synchro)
-{
-    gnss_synchro_ = gnss_synchro;
-    acquisition_->set_gnss_synchro(gnss_synchro_);
-}
-
-void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_channel(unsigned int channel)
-{
-    channel_ = channel;
-    acquisition_->set_channel(channel_);
+    attach_block(acquisition_.get(), in_streams, out_streams);
 }
 
 void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_local_code()
@@ -156,16 +103,5 @@ void GalileoE5aNoncoherentIQAcquisitionCafMI355X::set_local_code()
 
 float GalileoE5aNoncoherentIQAcquisitionCafMI355X::calculate_threshold(float pfa) const
 {
-    // (the reference's loop does not end with a zero step)
-    if (doppler_step_ == 0) throw std::invalid_argument(role_ + ": set_doppler_step before a pfa threshold");
-    unsigned int frequency_bins = 0;
-    for (int doppler = -static_cast<int>(doppler_max_); doppler <= static_cast<int>(doppler_max_);
-         doppler += static_cast<int>(doppler_step_))
-        frequency_bins++;
-    const unsigned int ncells = vector_length_ * frequency_bins;
-    const double exponent = 1 / static_cast<double>(ncells);
-    const double val = std::pow(1.0 - pfa, exponent);
-    const auto lambda = static_cast<double>(vector_length_);
-    // quantile(exponential_distribution(lambda), val) = -log1p(-val) / lambda
-    return static_cast<float>(-std::log1p(-val) / lambda);
+    return AcquisitionItemAdapterMI355X::calculate_threshold(pfa, vector_length_, static_cast<double>(vector_length_));
 }

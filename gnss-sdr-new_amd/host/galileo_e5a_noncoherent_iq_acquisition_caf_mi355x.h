@@ -21,11 +21,10 @@
 #include <string>
 #include <vector>
 
-#include "acquisition_interface.h"
-#include "configuration.h"
+#include "acquisition_item_adapter_mi355x.h"
 #include "galileo_e5a_noncoherent_iq_acquisition_caf_block_mi355x.h"
 
-class GalileoE5aNoncoherentIQAcquisitionCafMI355X : public AcquisitionInterface
+class GalileoE5aNoncoherentIQAcquisitionCafMI355X : public AcquisitionItemAdapterMI355X
 {
 public:
     GalileoE5aNoncoherentIQAcquisitionCafMI355X(const ConfigurationInterface* configuration, const std::string& role,
@@ -35,65 +34,29 @@ public:
     // throws std::invalid_argument with the reason where there is none to load.
     static void load_code_table(const ConfigurationInterface* configuration, const std::string& role);
 
-    std::string role() override { return role_; }
     std::string implementation() override { return "Galileo_E5a_Noncoherent_IQ_Acquisition_CAF_MI355X"; }
-    size_t item_size() override { return item_size_; }
 
-    void set_gnss_synchro(Gnss_Synchro* gnss_synchro) override;
-    void set_channel(unsigned int channel) override;
-    // the block publishes its events itself; the reference's adapter keeps no FSM either
-    void set_channel_fsm(std::weak_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = std::move(channel_fsm); }
-    void set_threshold(float threshold) override;
-    void set_doppler_max(unsigned int doppler_max) override;
-    void set_doppler_step(unsigned int doppler_step) override;
-    void init() override { acquisition_->init(); }
     // :212-262: the code period tiled coherent_integration_time_ms times, or followed by zeros
     void set_local_code() override;
-    void set_state(int state) override { acquisition_->set_state(state); }
-    signed int mag() override { return static_cast<signed int>(acquisition_->mag()); }
-    void reset() override { acquisition_->set_active(true); }
-    void stop_acquisition() override;
-    void set_resampler_latency(uint32_t latency_samples __attribute__((unused))) override {}
     // the exponential quantile with lambda = vector_length over vector_length * bins cells (:274-291)
-    float calculate_threshold(float pfa) const;
+    float calculate_threshold(float pfa) const override;
 
     // the gr::block the reference connects (get_right_block)
     galileo_e5a_noncoherentIQ_acquisition_caf_mi355x* get_block() { return acquisition_.get(); }
-    unsigned int vector_length() const { return vector_length_; }
-    unsigned int code_length() const { return code_length_; }
-    unsigned int sampled_ms() const { return sampled_ms_; }
-    unsigned int doppler_max() const { return doppler_max_; }
     unsigned int max_dwells() const { return max_dwells_; }
     int CAF_window_hz() const { return CAF_window_hz_; }
     int zero_padding() const { return Zero_padding; }
     bool bit_transition_flag() const { return bit_transition_flag_; }
     bool both_signal_components_flag() const { return both_signal_components; }
-    float threshold() const { return threshold_; }
 
 private:
-    const ConfigurationInterface* configuration_;
     std::unique_ptr<galileo_e5a_noncoherentIQ_acquisition_caf_mi355x> acquisition_;
-    std::weak_ptr<ChannelFsm> channel_fsm_;
-    Gnss_Synchro* gnss_synchro_{nullptr};
     std::vector<std::complex<float>> codeI_, codeQ_;
-    std::string item_type_;
-    std::string dump_filename_;
-    std::string role_;
-    int64_t fs_in_;
-    size_t item_size_{sizeof(std::complex<float>)};
-    float threshold_{0.0F};
     int Zero_padding;
     int CAF_window_hz_;
-    unsigned int doppler_max_;
-    unsigned int vector_length_{0};
-    unsigned int code_length_{0};
-    unsigned int channel_{0};
-    unsigned int doppler_step_{0};
-    unsigned int sampled_ms_;
     unsigned int max_dwells_;
     bool bit_transition_flag_;
     bool both_signal_components{false};
-    bool dump_;
 };
 
 #endif

@@ -6,7 +6,6 @@
 #include <stdexcept>
 
 #include "gnss_replicas.h"
-#include "gnss_sdr_flags.h"
 
 namespace
 {
@@ -17,19 +16,8 @@ constexpr double GPS_L1_CA_CODE_LENGTH_CHIPS = 1023.0;
 // gps_l1_ca_pcps_quicksync_acquisition.cc:36-145
 GpsL1CaPcpsQuickSyncAcquisitionMI355X::GpsL1CaPcpsQuickSyncAcquisitionMI355X(const ConfigurationInterface* configuration,
     const std::string& role, unsigned int in_streams, unsigned int out_streams, int device)
-    : configuration_(configuration), role_(role)
+    : AcquisitionItemAdapterMI355X(configuration, role, 2048000, 4, "./data/acquisition.dat")
 {
-    const std::string default_item_type("gr_complex");
-    const std::string default_dump_filename("./data/acquisition.dat");
-
-    item_type_ = configuration_->property(role + ".item_type", default_item_type);
-    const int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(2048000));
-    fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
-    dump_ = configuration_->property(role + ".dump", false);
-    doppler_max_ = static_cast<unsigned int>(configuration_->property(role + ".doppler_max", 5000));
-    if (FLAGS_doppler_max != 0) doppler_max_ = static_cast<unsigned int>(FLAGS_doppler_max);
-    sampled_ms_ = static_cast<unsigned int>(configuration_->property(role + ".coherent_integration_time_ms", 4));
-
     // -- Find number of samples per spreading code
     code_length_ = static_cast<unsigned int>(
         std::round(static_cast<double>(fs_in_) / (GPS_L1_CA_CODE_RATE_CPS / GPS_L1_CA_CODE_LENGTH_CHIPS)));
@@ -53,7 +41,6 @@ GpsL1CaPcpsQuickSyncAcquisitionMI355X::GpsL1CaPcpsQuickSyncAcquisitionMI355X(con
     vector_length_ = code_length_ * sampled_ms_;
     bit_transition_flag_ = configuration_->property(role + ".bit_transition_flag", false);
     max_dwells_ = bit_transition_flag_ ? 2U : static_cast<unsigned int>(configuration_->property(role + ".max_dwells", 1));
-    dump_filename_ = configuration_->property(role + ".dump_filename", default_dump_filename);
 
     // the block is made for items of sampled_ms code periods, its stream_to_vector delivers
     // folding_factor of them (:120-126): GNU Radio connects the two only when they agree
@@ -75,53 +62,9 @@ GpsL1CaPcpsQuickSyncAcquisitionMI355X::GpsL1CaPcpsQuickSyncAcquisitionMI355X(con
     conf.samples_per_code = static_cast<int32_t>(code_length_);
     conf.bit_transition_flag = bit_transition_flag_;
 
-    // the reference builds the gr_complex block only; any other item type gets a warning
-    item_size_ = sizeof(std::complex<float>);
-    if (item_type_ != "gr_complex") std::cerr << item_type_ << " unknown acquisition item type\n";
+    warn_item_type();
     acquisition_ = std::make_unique<pcps_quicksync_acquisition_mi355x>(conf, device);
-
-    if (in_streams > 1) std::cerr << "This implementation only supports one input stream\n";
-    if (out_streams > 0) std::cerr << "This implementation does not provide an output stream\n";
-}
-
-// :148-152
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::stop_acquisition()
-{
-    acquisition_->set_state(0);
-    acquisition_->set_active(false);
-}
-
-// :155-178: per-channel pfa, then the role's; without one, the configured threshold
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_threshold(float threshold)
-{
-    float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0F);
-    if (pfa == 0.0) pfa = configuration_->property(role_ + ".pfa", 0.0F);
-    threshold_ = pfa == 0.0 ? threshold : calculate_threshold(pfa);
-    acquisition_->set_threshold(threshold_);
-}
-
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_doppler_max(unsigned int doppler_max)
-{
-    doppler_max_ = doppler_max;
-    acquisition_->set_doppler_max(doppler_max_);
-}
-
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_doppler_step(unsigned int doppler_step)
-{
-    doppler_step_ = doppler_step;
-    acquisition_->set_doppler_step(doppler_step_);
-}
-
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_gnss_synchro(Gnss_Synchro* gnss_synchro)
-{
-    gnss_synchro_ = gnss_synchro;
-    acquisition_->set_gnss_synchro(gnss_synchro_);
-}
-
-void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_channel(unsigned int channel)
-{
-    channel_ = channel;
-    acquisition_->set_channel(channel_);
+    attach_block(acquisition_.get(), in_streams, out_streams);
 }
 
 // :227-243: one code period (sampled_ms / folding_factor = 1 copy)
@@ -136,16 +79,6 @@ void GpsL1CaPcpsQuickSyncAcquisitionMI355X::set_local_code()
 // :264-281: the exponential distribution's quantile with lambda = code_length / folding_factor
 float GpsL1CaPcpsQuickSyncAcquisitionMI355X::calculate_threshold(float pfa) const
 {
-    // (the reference's loop does not end with a zero step, :268)
-    if (doppler_step_ == 0) throw std::invalid_argument(role_ + ": set_doppler_step before a pfa threshold");
-    unsigned int frequency_bins = 0;
-    for (int doppler = -static_cast<int>(doppler_max_); doppler <= static_cast<int>(doppler_max_);
-         doppler += static_cast<int>(doppler_step_))
-        frequency_bins++;
-    const unsigned int ncells = (code_length_ / folding_factor_) * frequency_bins;
-    const double exponent = 1.0 / static_cast<double>(ncells);
-    const double val = std::pow(1.0 - pfa, exponent);
-    const double lambda = static_cast<double>(code_length_) / static_cast<double>(folding_factor_);
-    // quantile(exponential_distribution(lambda), val) = -log1p(-val) / lambda
-    return static_cast<float>(-std::log1p(-val) / lambda);
+    return AcquisitionItemAdapterMI355X::calculate_threshold(pfa, code_length_ / folding_factor_,
+        static_cast<double>(code_length_) / static_cast<double>(folding_factor_));
 }

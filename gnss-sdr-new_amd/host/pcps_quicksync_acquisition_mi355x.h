@@ -18,11 +18,9 @@
 
 #include <complex>
 #include <cstdint>
-#include <functional>
 #include <vector>
 
-#include "gnss_synchro.h"
-#include "gsdr.h"
+#include "acquisition_item_block_mi355x.h"
 
 // the arguments of pcps_quicksync_make_acquisition_cc
 struct QuickSync_Acq_Conf
@@ -37,78 +35,37 @@ struct QuickSync_Acq_Conf
     bool bit_transition_flag{false};
 };
 
-class pcps_quicksync_acquisition_mi355x
+class pcps_quicksync_acquisition_mi355x : public acquisition_item_block_mi355x
 {
 public:
     explicit pcps_quicksync_acquisition_mi355x(const QuickSync_Acq_Conf& conf, int device = 0);
-    ~pcps_quicksync_acquisition_mi355x();
-    pcps_quicksync_acquisition_mi355x(const pcps_quicksync_acquisition_mi355x&) = delete;
-    pcps_quicksync_acquisition_mi355x& operator=(const pcps_quicksync_acquisition_mi355x&) = delete;
 
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) { d_gnss_synchro = p_gnss_synchro; }
-    uint32_t mag() const { return static_cast<uint32_t>(d_mag); }
     // counts the Doppler bins and creates the grid (:160-196): here, the engine handle
-    void init();
+    void init() override;
     // :135-157: samples_per_code samples, unfolded
     void set_local_code(std::complex<float>* code);
-    void set_active(bool active) { d_active = active; }
-    void set_state(int32_t state);
-    void set_channel(uint32_t channel) { d_channel = channel; }
-    void set_threshold(float threshold) { d_threshold = threshold; }
-    void set_doppler_max(uint32_t doppler_max) { d_doppler_max = doppler_max; }
-    void set_doppler_step(uint32_t doppler_step) { d_doppler_step = doppler_step; }
-    void set_event_handler(std::function<void(int)> h) { d_events = std::move(h); }
-    // Ring path: the items work() is given are also samples [origin + d_sample_counter, ...)
-    // of the device ring, and state 1 reads its item there in place.
-    void set_ring(gsdr_stream* ring, uint64_t origin);
 
     // general_work: `in` holds ninput_items items of item_samples() samples; returns the items
     // consumed (consume_each).
     int work(const std::complex<float>* in, int ninput_items);
 
-    int state() const { return d_state; }
-    uint64_t sample_counter() const { return d_sample_counter; }
-    float threshold() const { return d_threshold; }
-    float test_statistics() const { return d_test_statistics; }
-    float input_power() const { return d_input_power; }
-    float mag_value() const { return d_mag; }
-    uint32_t num_doppler_bins() const { return d_num_doppler_bins; }
     uint32_t fft_size() const { return d_fft_size; }
-    uint32_t item_samples() const { return d_item; }
+    uint32_t item_samples() const { return d_item_samples; }
     uint32_t folding_factor() const { return d_folding_factor; }
     const gsdr_acq_quicksync_result& last_record() const { return d_last; }
 
 private:
     void upload_code();
-    void restart();
+    void restart_counters() override;
 
-    QuickSync_Acq_Conf d_conf;
-    int d_device;
-    gsdr_acq* d_engine{nullptr};
-    gsdr_stream* d_ring{nullptr};
-    uint64_t d_ring_origin{0};
-    Gnss_Synchro* d_gnss_synchro{nullptr};
-    std::function<void(int)> d_events;
     std::vector<std::complex<float>> d_code;
     gsdr_acq_quicksync_result d_last{};
-    uint64_t d_sample_counter{0};
-    float d_threshold{0.0F};
-    float d_mag{0.0F};
-    float d_input_power{0.0F};
-    float d_test_statistics{0.0F};
-    int32_t d_state{0};
-    uint32_t d_channel{0};
     uint32_t d_folding_factor;
-    uint32_t d_doppler_max;
-    uint32_t d_doppler_step{0};
     uint32_t d_max_dwells;
     uint32_t d_well_count{0};
     uint32_t d_samples_per_code;
     uint32_t d_fft_size;
-    uint32_t d_item;
-    uint32_t d_num_doppler_bins{0};
     bool d_bit_transition_flag;
-    bool d_active{false};
 };
 
 #endif

@@ -11,45 +11,10 @@
 // it emitted the sample counter, Prompt_I, Prompt_Q, correlation_length_ms and the flags;
 // beside them, per engine record that carried a valid output, the record's own prompt pair.
 #include <algorithm>
-#include <complex>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <exception>
-#include <fstream>
-#include <iostream>
-#include <string>
-#include <vector>
 
-#include "configuration.h"
-#include "gnss_block_factory_mi355x.h"
 #include "gnss_tracking_mi355x.h"
-#include "gsdr.h"
-
-namespace
-{
-std::string trim(const std::string& s)
-{
-    const auto a = s.find_first_not_of(" \t\r\n");
-    if (a == std::string::npos) return "";
-    return s.substr(a, s.find_last_not_of(" \t\r\n") - a + 1);
-}
-
-bool read_conf(const std::string& path, InMemoryConfiguration& config)
-{
-    std::ifstream f(path);
-    if (!f) return false;
-    std::string line;
-    while (std::getline(f, line))
-        {
-            line = trim(line.substr(0, line.find(';')));
-            const auto eq = line.find('=');
-            if (line.empty() || line[0] == '[' || eq == std::string::npos) continue;
-            config.set_property(trim(line.substr(0, eq)), trim(line.substr(eq + 1)));
-        }
-    return true;
-}
-}  // namespace
+#include "selftest_common.h"
 
 int main(int argc, char** argv)
 {
@@ -59,20 +24,8 @@ int main(int argc, char** argv)
             return 2;
         }
     InMemoryConfiguration config;
-    if (!read_conf(argv[1], config))
-        {
-            std::cerr << "cannot read " << argv[1] << '\n';
-            return 2;
-        }
-    std::ifstream f(argv[2], std::ios::binary | std::ios::ate);
-    if (!f)
-        {
-            std::cerr << "cannot read " << argv[2] << '\n';
-            return 2;
-        }
-    std::vector<std::complex<float>> x(static_cast<size_t>(f.tellg()) / sizeof(std::complex<float>));
-    f.seekg(0);
-    f.read(reinterpret_cast<char*>(x.data()), static_cast<std::streamsize>(x.size() * sizeof(std::complex<float>)));
+    std::vector<std::complex<float>> x;
+    if (!selftest::read_inputs(argv, config, x)) return 2;
     const std::string role = argv[3];
 
     std::unique_ptr<TrackingInterface> trk;
@@ -82,10 +35,7 @@ int main(int argc, char** argv)
         }
     catch (const std::exception& e)
         {
-            std::string what = e.what();
-            std::replace(what.begin(), what.end(), '"', '\'');
-            std::cout << "{\"built\": false, \"error\": \"" << what << "\"}\n";
-            return 1;
+            return selftest::report_error("built", e);
         }
     auto* adapter = dynamic_cast<GalileoE5aDllPllTrackingMI355X*>(trk.get());
     if (!adapter)

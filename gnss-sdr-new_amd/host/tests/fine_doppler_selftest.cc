@@ -9,44 +9,10 @@
 // block reads its 10 ms window there.  Prints one JSON line: per attempt the state before
 // every work() call, the items each call consumed, the event, and the Gnss_Synchro
 // acquisition fields afterwards.
-#include <complex>
-#include <cstdint>
-#include <cstdio>
 #include <cstdlib>
-#include <fstream>
-#include <iostream>
-#include <string>
-#include <vector>
 
-#include "configuration.h"
-#include "gnss_block_factory_mi355x.h"
 #include "gps_l1_ca_pcps_acquisition_fine_doppler_mi355x.h"
-#include "gsdr.h"
-
-namespace
-{
-std::string trim(const std::string& s)
-{
-    const auto a = s.find_first_not_of(" \t\r\n");
-    if (a == std::string::npos) return "";
-    return s.substr(a, s.find_last_not_of(" \t\r\n") - a + 1);
-}
-
-bool read_conf(const std::string& path, InMemoryConfiguration& config)
-{
-    std::ifstream f(path);
-    if (!f) return false;
-    std::string line;
-    while (std::getline(f, line))
-        {
-            line = trim(line.substr(0, line.find(';')));
-            const auto eq = line.find('=');
-            if (line.empty() || line[0] == '[' || eq == std::string::npos) continue;
-            config.set_property(trim(line.substr(0, eq)), trim(line.substr(eq + 1)));
-        }
-    return true;
-}
-}  // namespace
+#include "selftest_common.h"
 
 int main(int argc, char** argv)
 {
@@ -56,20 +22,8 @@ int main(int argc, char** argv)
             return 2;
         }
     InMemoryConfiguration config;
-    if (!read_conf(argv[1], config))
-        {
-            std::cerr << "cannot read " << argv[1] << '\n';
-            return 2;
-        }
-    std::ifstream f(argv[2], std::ios::binary | std::ios::ate);
-    if (!f)
-        {
-            std::cerr << "cannot read " << argv[2] << '\n';
-            return 2;
-        }
-    std::vector<std::complex<float>> x(static_cast<size_t>(f.tellg()) / sizeof(std::complex<float>));
-    f.seekg(0);
-    f.read(reinterpret_cast<char*>(x.data()), static_cast<std::streamsize>(x.size() * sizeof(std::complex<float>)));
+    std::vector<std::complex<float>> x;
+    if (!selftest::read_inputs(argv, config, x)) return 2;
     const uint32_t prn = static_cast<uint32_t>(std::atoi(argv[3]));
     const float threshold = static_cast<float>(std::atof(argv[4]));
     const int attempts = std::atoi(argv[5]);
@@ -82,12 +36,8 @@ int main(int argc, char** argv)
             std::cout << "{\"built\": false}\n";
             return 1;
         }
-    auto* adapter = dynamic_cast<GpsL1CaPcpsAcquisitionFineDopplerMI355X*>(acq.get());
-    if (!adapter)
-        {
-            std::cout << "{\"built\": true, \"implementation\": \"" << acq->implementation() << "\", \"fine\": false}\n";
-            return 1;
-        }
+    auto* adapter = selftest::expect_adapter<GpsL1CaPcpsAcquisitionFineDopplerMI355X>(acq.get(), "fine");
+    if (!adapter) return 1;
     pcps_acquisition_fine_doppler_mi355x* block = adapter->get_block();
     Gnss_Synchro synchro;
     synchro.System = 'G';
@@ -111,12 +61,8 @@ int main(int argc, char** argv)
     gsdr_stream* ring = nullptr;
     if (use_ring)
         {
-            if (gsdr_stream_create(0, GSDR_ITEM_GR_COMPLEX, x.size(), 10ull * N, &ring) != GSDR_OK ||
-                gsdr_stream_push(ring, x.data(), 0, x.size()) != GSDR_OK)
-                {
-                    std::cerr << "ring: " << gsdr_last_error() << '\n';
-                    return 1;
-                }
+            ring = selftest::make_ring(x, 10ull * N);
+            if (!ring) return 1;
             block->set_ring(ring, 0);
         }
 
