@@ -261,6 +261,7 @@ struct TrkConst
     CfConst cf_narrow;
     int32_t high_dyn, smoother_length;  // Dll_Pll_Conf::high_dyn / smoother_length (dll_pll_conf.h:62,80)
     int32_t interchange_iq;  // d_interchange_iq (:242, :310): Prompt_I / Prompt_Q swapped on output
+    double kf_beta;          // Kalman loop: d_beta = d_code_chip_rate / d_signal_carrier_freq (kf_tracking.cc:448)
 };
 
 // Mutable scalar loop state (dll_pll_veml_tracking.h:117-209 minus the
@@ -290,6 +291,17 @@ struct TrkHot
     float log_err[4];
 };
 
+// Kalman loop (kf_tracking.h:121-130): the filter's state of one channel.  d_F and d_H are
+// functions of d_current_correlation_time_s (TrkHot::corr_time) alone and are rebuilt from
+// it every call (kf_model); d_R is diagonal.
+struct TrkKf
+{
+    double x[4];   // d_x_old_old: code-phase error [chips], carrier phase [rad], Doppler [Hz], rate [Hz/s]
+    double P[16];  // d_P_old_old, row-major
+    double Q[16];  // d_Q (update_kf_narrow_integration_time replaces it)
+    double R[2];   // d_R(0,0), d_R(1,1)
+};
+
 // Device-memory image of the mutable part of one channel.
 struct TrkChan
 {
@@ -299,6 +311,7 @@ struct TrkChan
     // high_dyn: the two boost::circular_buffer<pair<double,double>> of capacity
     // 2*smoother_length (:554-563), pushed together (same sample count)
     double hist_carr[2 * kMaxSmoother], hist_code[2 * kMaxSmoother], hist_samples[2 * kMaxSmoother];
+    TrkKf kf;  // Kalman mode only (gsdr_trk_set_kf)
 };
 
 // The loop state make_prep reads (wave 0 -> wave 1 after the locked branch): wave 1 plans
@@ -480,6 +493,12 @@ __device__ __forceinline__ void seq_sums(const float* terms, int stride, int n, 
 // sums in element order through `scratch` (3 x kMaxCn0 floats of LDS).  Returns 0 on a
 // loss of lock, 1 while the prompt buffer fills, 2 with a full buffer: then the EVM
 // (:1027-1053, an output only) is the one wave 1 computes (evm_of).
+// CR: the Kalman loop's form.  Its filter integrates what the float library functions of a
+// call return without decay (x(1) never wraps, and in a replay nothing feeds back), so a last
+// place of log10f, atanf or hypotf, which no two libraries agree on, stays in x and P for
+// good.  There these functions are evaluated correctly rounded -- in double, rounded to
+// float -- which is one definite value on every platform (kf_restatement.py does the same).
+template <bool CR = false>
 __device__ inline int cn0_and_lock(const TrkConst& c, TrkHot& t, float2* pbuf, float (*scratch)[kMaxCn0], double coh,
     int lane)
 {
@@ -516,7 +535,11 @@ __device__ inline int cn0_and_lock(const TrkConst& c, TrkHot& t, float2* pbuf, f
         snr = psig / (m2 - psig);
     else
         snr = aux / (m2 - aux);
-    const float raw = 10.0F * log10f(snr) - 10.0F * log10f((float)coh);
+    float raw;
+    if constexpr (CR)
+        raw = 10.0F * (float)log10((double)snr) - 10.0F * (float)log10((double)(float)coh);
+    else
+        raw = 10.0F * log10f(snr) - 10.0F * log10f((float)coh);
     t.cn0_db_hz = (double)sm_smooth(c.sm[0], t, 0, raw);
     // carrier_lock_detector(buffer, 1): element 0 only
     const float si = 0.0F + lane_f(ei.x, 0), sq = 0.0F + lane_f(ei.y, 0);
@@ -632,6 +655,9 @@ __device__ inline double hist_rate(const double* v, const double* s, int head, i
 
 // Every lane of wave 0 runs this with uniform values; the history stores write
 // the same value from every lane.
+// KF: kf_tracking::update_tracking_vars (kf_tracking.cc:1237-1313), the same but for the
+// accumulated carrier phase, from which it subtracts the float remnant (:1279-1284)
+template <bool KF = false>
 __device__ inline void update_tracking_vars(const TrkConst& c, TrkHot& t, TrkChan* gc)  // :1216-1287
 {
     const double T_chip = 1.0 / t.code_freq_chips;
@@ -664,7 +690,11 @@ __device__ inline void update_tracking_vars(const TrkConst& c, TrkHot& t, TrkCha
     const double len = (double)t.current_prn_length_samples;
     t.rem_carr_phase_rad += (float)(t.carrier_phase_step_rad * len + 0.5 * t.carrier_phase_rate_step_rad * len * len);
     t.rem_carr_phase_rad = (float)fmod((double)t.rem_carr_phase_rad, kTwoPi);
-    t.acc_carrier_phase_rad -= (t.carrier_phase_step_rad * len + 0.5 * t.carrier_phase_rate_step_rad * len * len);
+    if constexpr (KF)
+        t.acc_carrier_phase_rad -=
+            (double)(float)(t.carrier_phase_step_rad * len + 0.5 * t.carrier_phase_rate_step_rad * len * len);
+    else
+        t.acc_carrier_phase_rad -= (t.carrier_phase_step_rad * len + 0.5 * t.carrier_phase_rate_step_rad * len * len);
     t.code_phase_step_chips = t.code_freq_chips / c.fs_in;
     if (c.high_dyn)
         {
@@ -868,6 +898,151 @@ struct DllSpec  // wave 3's code loop of a call
     float log_err2, log_err3;
 };
 
+// ------------------------------------------------------------------ Kalman loop
+// run_Kf (kf_tracking.cc:1129-1204) on wave 1, the covariance algebra spread over its
+// lanes: lane l (mod 16) owns element (i, j) = (l / 4, l % 4) of every 4x4 matrix, the
+// 4x2 and 2x2 ones sit on the lanes with j < 2 (and i < 2); a product's other operands
+// come through cross-lane reads.  d_F = I + five entries above the diagonal and d_H =
+// [I2 | four entries], so each product is the lane's own element and two terms (kf_model
+// holds the nine entries); FP64 as the reference's arma::mat; the 2x2 inverse in closed
+// form.  x (4 values) is uniform across the lanes.
+struct KfModel
+{
+    double f02, f03, f12, f13, f23;  // d_F (init_kf, :863-866)
+    double h02, h03, h12, h13;       // d_H (:868-869)
+};
+
+__host__ __device__ inline KfModel kf_model(double beta, double Ti)
+{
+    const double TiTi = Ti * Ti;
+    return KfModel{beta * Ti, beta * TiTi / 2.0, 2.0 * kGnssPi * Ti, kGnssPi * TiTi, Ti, -beta * Ti / 2.0, beta * TiTi / 6.0,
+        -kGnssPi * Ti, kGnssPi * TiTi / 3.0};
+}
+
+// d_R from a C/N0 (update_kf_cn0, :947-954; update_kf_narrow_integration_time, :921-927)
+__host__ __device__ inline void kf_r_of_cn0(double cn0_db_hz, double Ti, float spc_f, double (&R)[2])
+{
+    const double spc = (double)spc_f;
+    const double CN0_lin = pow(10.0, cn0_db_hz / 10.0);
+    const double CN0_lin_Ti = CN0_lin * Ti;
+    const double Sigma2_Phase = (1.0 / (2.0 * CN0_lin_Ti)) * (1.0 + 1.0 / (2.0 * CN0_lin_Ti));
+    const double Sigma2_Tau = (1.0 / CN0_lin_Ti) * (spc + (spc / (1.0 - spc)) * (1.0 / (2.0 * CN0_lin_Ti)));
+    R[0] = Sigma2_Tau;
+    R[1] = Sigma2_Phase;
+}
+
+__device__ __forceinline__ double lane_d(double v, int i)  // i uniform
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, i);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), i);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// element (i, j) of F X F^T from the lane's element x of X: A = F X takes rows 2 and 3 of
+// X in the lane's column, A F^T columns 2 and 3 of A in the lane's row
+__device__ __forceinline__ double kf_fxft(const KfModel& m, double x, int i, int j)
+{
+    const double fi2 = i == 0 ? m.f02 : (i == 1 ? m.f12 : 0.0);
+    const double fi3 = i == 0 ? m.f03 : (i == 1 ? m.f13 : (i == 2 ? m.f23 : 0.0));
+    const double fj2 = j == 0 ? m.f02 : (j == 1 ? m.f12 : 0.0);
+    const double fj3 = j == 0 ? m.f03 : (j == 1 ? m.f13 : (j == 2 ? m.f23 : 0.0));
+    const double a = x + fi2 * __shfl(x, 8 + j) + fi3 * __shfl(x, 12 + j);
+    return a + fj2 * __shfl(a, 4 * i + 2) + fj3 * __shfl(a, 4 * i + 3);
+}
+
+// The discriminators of run_Kf (:1131-1151) with their float library calls correctly
+// rounded (see cn0_and_lock): pll_cloop_two_quadrant_atan / pll_four_quadrant_atan and
+// dll_nc_e_minus_l_normalized; dll_nc_vemlp calls none
+[[maybe_unused]] __device__ inline double kf_carrier_disc(int cloop, float2 p)
+{
+    if (!cloop) return (double)(float)atan2((double)p.y, (double)p.x);
+    if (p.x != 0.0F) return (double)(float)atan((double)(p.y / p.x));
+    return 0.0;
+}
+
+[[maybe_unused]] __device__ inline double kf_dll_nc_e_minus_l(float2 e, float2 l, float spc, float slope, float y)
+{
+    // the products of floats are exact in double: one rounding in the sum, one in the root
+    const double pe = (double)(float)sqrt((double)e.x * (double)e.x + (double)e.y * (double)e.y);
+    const double pl = (double)(float)sqrt((double)l.x * (double)l.x + (double)l.y * (double)l.y);
+    const double s = pe + pl;
+    if (s == 0.0) return 0.0;
+    return (double)((y - slope * spc) / slope) * (pe - pl) / s;
+}
+
+struct KfSlot  // x and P of a channel: the current one and the one wave 1 steps into
+{
+    double x[4], P[16];
+};
+
+struct KfPred
+{
+    double xm[4];  // d_x_new_old
+    double Pm;     // d_P_new_old(i, j)
+    double M;      // (d_P_new_old * d_H.t())(i, j), lanes with j < 2
+    double HP;     // (d_H * d_P_new_old)(i, j), lanes with i < 2
+};
+
+// Prediction, P- H^T and H P- (:1156-1158 and the first products of :1162): nothing here
+// depends on the call's lock test.  Every product sums its terms in ascending index with two
+// roundings per term, as Armadillo's fixed-size 4x4 code does without FMA (the terms F and H
+// make zero change nothing), so the step is the restatement's bit for bit.
+[[maybe_unused]] __device__ __forceinline__ KfPred kf_predict(const KfModel& m, const KfSlot& s, const double* Q, int lane)
+{
+    const int l = lane & 15, i = l >> 2, j = l & 3;
+    KfPred r;
+    const double x0 = s.x[0], x1 = s.x[1], x2 = s.x[2], x3 = s.x[3];
+    r.xm[0] = x0 + m.f02 * x2 + m.f03 * x3;
+    r.xm[1] = x1 + m.f12 * x2 + m.f13 * x3;
+    r.xm[2] = x2 + m.f23 * x3;
+    r.xm[3] = x3;
+    r.Pm = kf_fxft(m, s.P[l], i, j) + Q[l];
+    const double hj2 = j == 0 ? m.h02 : m.h12, hj3 = j == 0 ? m.h03 : m.h13;
+    r.M = r.Pm + hj2 * __shfl(r.Pm, 4 * i + 2) + hj3 * __shfl(r.Pm, 4 * i + 3);
+    const double hi2 = i == 0 ? m.h02 : m.h12, hi3 = i == 0 ? m.h03 : m.h13;
+    r.HP = r.Pm + hi2 * __shfl(r.Pm, 8 + j) + hi3 * __shfl(r.Pm, 12 + j);
+    return r;
+}
+
+// The lane's row of the Kalman gain, K = M inv(H M + R) (:1162), and x = x- + K z (:1164)
+[[maybe_unused]] __device__ __forceinline__ void kf_gain(const KfModel& m, const KfPred& p, const double (&R)[2], double z0, double z1, int lane,
+    double (&K)[2], double (&xn)[4])
+{
+    const int l = lane & 15, i = l >> 2, j = l & 3;
+    // S = (H P-) H^T + R, associated as the reference's expression is
+    const double hj2 = j == 0 ? m.h02 : m.h12, hj3 = j == 0 ? m.h03 : m.h13;
+    const double rij = i == j ? (i == 0 ? R[0] : R[1]) : 0.0;
+    const double s = p.HP + hj2 * __shfl(p.HP, 4 * i + 2) + hj3 * __shfl(p.HP, 4 * i + 3) + rij;  // lanes 0, 1, 4, 5
+    const double s00 = lane_d(s, 0), s01 = lane_d(s, 1), s10 = lane_d(s, 4), s11 = lane_d(s, 5);
+    const double det = s00 * s11 - s01 * s10;
+    const double v00 = s11 / det, v01 = -s01 / det, v10 = -s10 / det, v11 = s00 / det;
+    const double mi0 = __shfl(p.M, 4 * i), mi1 = __shfl(p.M, 4 * i + 1);
+    K[0] = mi0 * v00 + mi1 * v10;
+    K[1] = mi0 * v01 + mi1 * v11;
+    const double kz = K[0] * z0 + K[1] * z1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xn[q] = p.xm[q] + lane_d(kz, 4 * q);
+}
+
+// P(i, j) = ((I - K H) P-)(i, j) (:1166): the lane's row of I - K H times its column of P-
+[[maybe_unused]] __device__ __forceinline__ double kf_cov(const KfModel& m, const KfPred& p, const double (&K)[2], int lane)
+{
+    const int l = lane & 15, i = l >> 2, j = l & 3;
+    const double g0 = (i == 0 ? 1.0 : 0.0) - K[0];
+    const double g1 = (i == 1 ? 1.0 : 0.0) - K[1];
+    const double g2 = (i == 2 ? 1.0 : 0.0) - (K[0] * m.h02 + K[1] * m.h12);
+    const double g3 = (i == 3 ? 1.0 : 0.0) - (K[0] * m.h03 + K[1] * m.h13);
+    return g0 * __shfl(p.Pm, j) + g1 * __shfl(p.Pm, 4 + j) + g2 * __shfl(p.Pm, 8 + j) + g3 * __shfl(p.Pm, 12 + j);
+}
+
+struct KfSpec  // wave 1's filter step of a call, as far as wave 0's loop update needs it
+{
+    double code_error_kf_chips, carrier_phase_kf_rad, carrier_doppler_kf_hz;
+    double R[2];
+    float log_err[4];
+};
+
 struct SpecLink
 {
     DllPllSpec* res;   // LDS
@@ -878,6 +1053,53 @@ struct SpecLink
     int* lfi_lds;      // LDS: the current slot (read by wave 3 at the start of a call)
     int lfi;           // wave 0: the current slot
     int e;             // wave 0: this call's index
+};
+
+// The Kalman loop's LDS: x / P in two slots (wave 1 steps from the current one into the
+// other, wave 0 switches when the call stays locked), d_Q, d_R's diagonal and wave 1's
+// results; 528 bytes, allocated for the KF kernel instances only
+struct KfShared
+{
+    KfSlot slot[2];
+    double q[16], r[2];
+    KfSpec spec;
+    int cur;
+};
+
+template <bool KF>
+struct KfWave0  // wave 0's locals of a call in the Kalman loop; none in the DLL/PLL kernels
+{
+};
+
+template <bool KF>
+__device__ __forceinline__ KfShared* kf_shared()
+{
+    if constexpr (KF)
+        {
+            __shared__ KfShared s;
+            return &s;
+        }
+    else
+        return nullptr;
+}
+
+struct KfLink  // the Kalman loop's SpecLink (take_kf, kf_narrow)
+{
+    const KfSpec* res;   // LDS: wave 1's filter step of the call
+    int* ready;          // LDS: the call index whose step res holds
+    double* kfq;         // LDS: d_Q
+    const Cn0Spec* cn0;  // LDS: wave 2's lock test of the call
+    int* cn0_e;
+    int kfi;             // wave 0: the current x / P slot
+    int e;               // wave 0: this call's index
+    double R[2];         // wave 0: the call's d_R, stored when the call stays locked
+};
+
+template <>
+struct KfWave0<true>
+{
+    int kfi0;   // the x / P slot current at the call's start
+    KfLink kl;
 };
 
 __device__ inline void take_dll_pll(const TrkConst& c, TrkHot& t, SpecLink& sl)
@@ -899,6 +1121,47 @@ __device__ inline void take_dll_pll(const TrkConst& c, TrkHot& t, SpecLink& sl)
     t.log_err[3] = d.log_err3;
     if (c.carrier_aiding) t.code_freq_chips += t.carrier_doppler_hz * c.code_chip_rate / c.signal_carrier_freq;
     sl.lfi ^= 1;  // wave 3 filtered into the other slot
+}
+
+// The rest of run_Kf (:1168-1203) from wave 1's filter step: the NCO commands
+[[maybe_unused]] __device__ inline void take_kf(const TrkConst& c, TrkHot& t, KfLink& sl)
+{
+    while (__hip_atomic_load(sl.ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != sl.e)
+        __builtin_amdgcn_s_sleep(1);
+    const KfSpec r = *sl.res;
+    t.carrier_doppler_hz = r.carrier_doppler_kf_hz;
+    t.P_accu_old = t.P_accu;
+    t.code_freq_chips = c.code_chip_rate + r.carrier_doppler_kf_hz * c.code_chip_rate / c.signal_carrier_freq;
+    t.rem_code_phase_samples += c.fs_in * r.code_error_kf_chips / t.code_freq_chips;
+    t.rem_carr_phase_rad = (float)r.carrier_phase_kf_rad;
+    for (int i = 0; i < 4; ++i) t.log_err[i] = r.log_err[i];
+    sl.R[0] = r.R[0];
+    sl.R[1] = r.R[1];
+    sl.kfi ^= 1;  // wave 1 stepped into the other slot
+}
+
+// update_kf_narrow_integration_time (:898-935) at the switch to the extended correlator:
+// d_Q summed over extend_correlation_symbols steps of the old d_F (d_Q itself replaced
+// in the loop), d_R from this call's C/N0 with the new Ti and the still wide spc; d_F and
+// d_H follow t.corr_time.  Once per channel, on wave 0's lanes like the per-call algebra.
+[[maybe_unused]] __device__ inline void kf_narrow(const TrkConst& c, const TrkHot& t, KfLink& sl, double Ti_old, int lane)
+{
+    const int l = lane & 15, i = l >> 2, j = l & 3;
+    // the branch this runs in is void on a loss of lock (the caller rebuilds the call):
+    // nothing is written then
+    while (__hip_atomic_load(sl.cn0_e, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != sl.e)
+        __builtin_amdgcn_s_sleep(1);
+    if (!sl.cn0->locked) return;
+    const KfModel m = kf_model(c.kf_beta, Ti_old);
+    double q = sl.kfq[l], qnew = 0.0;
+    for (int n = 0; n < c.extend_correlation_symbols; ++n)
+        {
+            q = kf_fxft(m, q, i, j);
+            qnew += q;
+        }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 16) sl.kfq[lane] = qnew;
+    kf_r_of_cn0(sl.cn0->cn0_db_hz, t.corr_time, t.spc, sl.R);
 }
 
 // The call's accumulators before the lock test (states 2 and 4, :1828-1845 / :2032):
@@ -935,7 +1198,11 @@ __device__ __forceinline__ void init_out(EpochOut& o)
 
 // States 2 and 4 run the branch of a call that stays locked; the lock test's results
 // come from wave 2 (Cn0Spec) and the caller undoes the branch on a loss of lock.
-__device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* gc, SpecLink& sl,
+// KF: the state machine of kf_tracking::general_work (kf_tracking.cc:1833-2066), which is
+// this one with run_Kf in run_dll_pll's place, its own update_tracking_vars and
+// update_kf_narrow_integration_time where the DLL/PLL block narrows its loop filters
+template <bool KF = false, typename Link = SpecLink>
+__device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* gc, Link& sl,
     const float2 (&taps)[kMaxTrkTaps + 1], const float2 (&epl)[3], uint64_t nitems_read, EpochOut& o, bool tm,
     uint64_t (&pr)[3])
 {
@@ -946,9 +1213,12 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
             tprobe(tm, pr, 0);
                 {
                     int next_state = 0;
-                    take_dll_pll(c, t, sl);
+                    if constexpr (KF)
+                        take_kf(c, t, sl);
+                    else
+                        take_dll_pll(c, t, sl);
                     tprobe(tm, pr, 1);
-                    update_tracking_vars(c, t, gc);
+                    update_tracking_vars<KF>(c, t, gc);
                     tprobe(tm, pr, 2);
                     log_point(c, t, o);
                     if (!t.pull_in_transitory)
@@ -973,13 +1243,23 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
                                 {
                                     // extended correlator: narrow loops and taps (:1945-1983)
                                     t.extend_count = 0;
-                                    t.corr_time = c.corr_time_ext;
-                                    t.state = 3;
-                                    LoopFilter& lf = sl.lfs[sl.lfi];
-                                    lf.T = (float)t.corr_time;
-                                    lf_update(lf);
-                                    lf.bw = c.dll_bw_narrow_hz;
-                                    lf_update(lf);
+                                    if constexpr (KF)
+                                        {
+                                            const double Ti_old = t.corr_time;
+                                            t.corr_time = c.corr_time_ext;
+                                            t.state = 3;
+                                            kf_narrow(c, t, sl, Ti_old, (int)(threadIdx.x & 63));
+                                        }
+                                    else
+                                        {
+                                            t.corr_time = c.corr_time_ext;
+                                            t.state = 3;
+                                            LoopFilter& lf = sl.lfs[sl.lfi];
+                                            lf.T = (float)t.corr_time;
+                                            lf_update(lf);
+                                            lf.bw = c.dll_bw_narrow_hz;
+                                            lf_update(lf);
+                                        }
                                     t.narrow = 1;
                                     t.spc = c.early_late_space_narrow_chips;
                                 }
@@ -991,7 +1271,7 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
     else if (t.state == 3)  // coherent integration (:1989-2026)
         {
             save_correlation_results(c, t, taps, epl);
-            update_tracking_vars(c, t, gc);
+            update_tracking_vars<KF>(c, t, gc);
             if (t.current_data_symbol == 0)
                 {
                     log_point(c, t, o);
@@ -1012,9 +1292,12 @@ __device__ inline void after_correlation(const TrkConst& c, TrkHot& t, TrkChan* 
             pre_lock(c, t, taps, epl, nitems_read);
             tprobe(tm, pr, 0);
                 {
-                    take_dll_pll(c, t, sl);
+                    if constexpr (KF)
+                        take_kf(c, t, sl);
+                    else
+                        take_dll_pll(c, t, sl);
                     tprobe(tm, pr, 1);
-                    update_tracking_vars(c, t, gc);
+                    update_tracking_vars<KF>(c, t, gc);
                     tprobe(tm, pr, 2);
                     if (!t.acc_carrier_phase_initialized)
                         {
@@ -1543,7 +1826,11 @@ __device__ __forceinline__ Prep make_prep(const TrkConst& c, const TrkHot& t, bo
 // period +-1 sample), so the update hides the HBM latency.
 // PACK: every channel of the launch tracks a pilot on the compact replica (see
 // correlate_chunk); the handle launches it instead when its replicas qualify.
-template <int IT, bool PACK = false>
+// KF: the Kalman loop (gsdr_trk_set_kf) in the DLL/PLL loop's place: wave 1 runs the
+// discriminators, the prediction and P- H^T as soon as the accumulators are known and, in
+// state 4 only, waits for wave 2's C/N0 where d_R enters the innovation covariance; wave 0
+// takes x for the NCO commands while wave 1 finishes P; wave 3 has no code loop to run.
+template <int IT, bool PACK = false, bool KF = false>
 __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __restrict__ consts,
     TrkChan* __restrict__ chans, const float* const* __restrict__ codes, const float* const* __restrict__ data_codes,
     const void* __restrict__ iq, uint64_t iq_first, uint64_t iq_items, uint32_t max_epochs, gsdr_trk_epoch* __restrict__ out,
@@ -1587,6 +1874,15 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const TrkConst& c = consts[ch];
     TrkChan* gc = chans + ch;
+    if constexpr (KF)
+        {
+            KfShared* const ks = kf_shared<true>();
+            if (tid < 16) ks->slot[0].P[tid] = gc->kf.P[tid];
+            if (tid < 16) ks->q[tid] = gc->kf.Q[tid];
+            if (tid < 4) ks->slot[0].x[tid] = gc->kf.x[tid];
+            if (tid < 2) ks->r[tid] = gc->kf.R[tid];
+            if (tid == 0) ks->cur = 0;
+        }
     // The tracking loop is a latency chain that shares its CUs with the
     // acquisition grid running on another queue: raise the issue priority.
     __builtin_amdgcn_s_setprio(3);
@@ -1782,7 +2078,7 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
 #pragma unroll
                 for (int q = 0; q < 3; ++q) epl[q] = make_float2(lane_f(mine.x, ix[q]), lane_f(mine.y, ix[q]));
             };
-            if (wave == 3)
+            if (!KF && wave == 3)
                 {
                     // this call's code loop (DLL discriminator and filter) on a copy of
                     // the state, into the code loop filter slot that is not current; wave
@@ -1918,8 +2214,53 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                                 }
                             else
                                 save_correlation_results(c, t1, taps, epl);
-                            run_pll(c, t1);
-                            if (lane == 0)
+                            if constexpr (KF)
+                                {
+                                    // run_Kf (:1129-1166): discriminators, prediction and
+                                    // P- H^T; then d_R -- in state 4 update_kf_cn0's, from
+                                    // the C/N0 of this call's lock test (wave 2)
+                                    KfShared* const ks = kf_shared<true>();
+                                    const int cur = ks->cur;
+                                    const KfModel km = kf_model(c.kf_beta, t1.corr_time);
+                                    const double disc_hz = kf_carrier_disc(t1.cloop, t1.P_accu) / kTwoPi;
+                                    const double disc_chips = c.veml ? dll_nc_vemlp(t1.VE_accu, t1.E_accu, t1.L_accu, t1.VL_accu)
+                                                                     : kf_dll_nc_e_minus_l(t1.E_accu, t1.L_accu, t1.spc, 1.0F, 1.0F);
+                                    const KfPred kp = kf_predict(km, ks->slot[cur], ks->q, lane);
+                                    double R[2] = {ks->r[0], ks->r[1]};
+                                    if (t1.state == 4)
+                                        {
+                                            while (__hip_atomic_load(&s_cn0_e, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) !=
+                                                   (int)e)
+                                                __builtin_amdgcn_s_sleep(1);
+                                            kf_r_of_cn0(s_cn0.cn0_db_hz, t1.corr_time, t1.spc, R);
+                                        }
+                                    double K[2], xn[4];
+                                    kf_gain(km, kp, R, disc_chips, disc_hz * kTwoPi, lane, K, xn);
+                                    if (lane == 0)
+                                        {
+                                            KfSpec r;
+                                            r.code_error_kf_chips = xn[0];
+                                            r.carrier_phase_kf_rad = xn[1];
+                                            r.carrier_doppler_kf_hz = xn[2];
+                                            r.R[0] = R[0];
+                                            r.R[1] = R[1];
+                                            r.log_err[0] = (float)disc_hz;
+                                            r.log_err[1] = (float)xn[2];
+                                            r.log_err[2] = (float)disc_chips;
+                                            r.log_err[3] = (float)xn[0];
+                                            ks->spec = r;
+                                            __hip_atomic_store(&s_spec_e, (int)e, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                        }
+                                    // off wave 0's path: the covariance, and the step into the
+                                    // other slot (d_x_new_new(0) = 0, :1170)
+                                    const double pn = kf_cov(km, kp, K, lane);
+                                    KfSlot& nx = ks->slot[cur ^ 1];
+                                    if (lane < 16) nx.P[lane] = pn;
+                                    if (lane < 4) nx.x[lane] = lane == 0 ? 0.0 : (lane == 1 ? xn[1] : (lane == 2 ? xn[2] : xn[3]));
+                                }
+                            else
+                                run_pll(c, t1);
+                            if (!KF && lane == 0)
                                 {
                                     DllPllSpec r;
                                     r.carrier_doppler_hz = t1.carrier_doppler_hz;
@@ -1935,7 +2276,7 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                             // wave 0 takes for the record when the call stays locked: the
                             // buffer's other elements and this call's prompt (wave 2 writes
                             // only this call's element)
-                            if (t1.cn0_estimation_counter >= c.cn0_samples)
+                            if (!KF && t1.cn0_estimation_counter >= c.cn0_samples)  // kf_tracking has no EVM
                                 {
                                     const double evm = evm_of(c, t1.cn0_estimation_counter, t1.P_accu, s_pbuf, s_evm_buf, lane);
                                     if (lane == 0)
@@ -1991,7 +2332,7 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                                 t2.state == 2 ? c.code_period : c.code_period * (double)c.extend_correlation_symbols;
                             pre_lock(c, t2, taps, epl, n_read);
                             if (timing && lane == 0) s_w2t[0] = wall_clock64();
-                            const int locked = cn0_and_lock(c, t2, s_pbuf, s_cn, coh, lane);
+                            const int locked = cn0_and_lock<KF>(c, t2, s_pbuf, s_cn, coh, lane);
                             if (lane == 0)
                                 {
                                     if (timing) s_w2t[1] = wall_clock64();
@@ -2023,7 +2364,17 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                     uint64_t tm3 = 0;
                     if (timing) tm3 = wall_clock64();
                     SpecLink sl{&s_spec, &s_dspec, &s_dspec_e, &s_spec_e, s_lfs, &s_lfi, lfi0, (int)e};
-                    after_correlation(c, t, gc, sl, taps, epl, n_read, o, timing != nullptr, pr);
+                    KfWave0<KF> kw;
+                    (void)kw;
+                    if constexpr (KF)
+                        {
+                            KfShared* const ks = kf_shared<true>();
+                            kw.kfi0 = ks->cur;
+                            kw.kl = KfLink{&ks->spec, &s_spec_e, ks->q, &s_cn0, &s_cn0_e, kw.kfi0, (int)e, {0.0, 0.0}};
+                            after_correlation<true>(c, t, gc, kw.kl, taps, epl, n_read, o, timing != nullptr, pr);
+                        }
+                    else
+                        after_correlation(c, t, gc, sl, taps, epl, n_read, o, timing != nullptr, pr);
                     t.next_sample = n_read + (uint64_t)(int64_t)t.current_prn_length_samples;
                     // the next call's plan (the window / chunk-0 prefetch of this iteration
                     // starts at nb): states 2 / 4 on wave 1 from the state published here,
@@ -2063,7 +2414,7 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                             if (r.locked)
                                 {
                                     cn0_apply(t, r);
-                                    o.evm = r.locked == 2;
+                                    o.evm = !KF && r.locked == 2;
                                 }
                             else
                                 {
@@ -2077,7 +2428,19 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                                         t.pull_in_transitory = 0;
                                     pre_lock(c, t, taps, epl, n_read);
                                     cn0_apply(t, r);
-                                    clear_tracking_vars(t);
+                                    if constexpr (KF)
+                                        {
+                                            // kf_tracking::clear_tracking_vars (:1217-1233) leaves
+                                            // the discriminator and filter outputs that log_data
+                                            // dumps as they are; the filter step is dropped
+                                            float le[4];
+                                            for (int i = 0; i < 4; ++i) le[i] = t.log_err[i];
+                                            clear_tracking_vars(t);
+                                            for (int i = 0; i < 4; ++i) t.log_err[i] = le[i];
+                                            kw.kl.kfi = kw.kfi0;
+                                        }
+                                    else
+                                        clear_tracking_vars(t);
                                     if (c.track_pilot) t.P_data_accu = make_float2(0.f, 0.f);
                                     t.state = 0;
                                     init_out(o);
@@ -2091,6 +2454,19 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
                         {
                             lfi0 = sl.lfi;
                             if (lane == 0) s_lfi = lfi0;
+                        }
+                    if constexpr (KF)
+                        {
+                            if (kw.kl.kfi != kw.kfi0)
+                                {
+                                    if (lane == 0)
+                                        {
+                                            KfShared* const ks = kf_shared<true>();
+                                            ks->cur = kw.kl.kfi;
+                                            ks->r[0] = kw.kl.R[0];
+                                            ks->r[1] = kw.kl.R[1];
+                                        }
+                                }
                         }
                     uint64_t tevm0 = 0, tevm1 = 0;
                     if (o.evm)
@@ -2183,7 +2559,37 @@ __global__ void __launch_bounds__(kTrkThreads) trk_kernel(const TrkConst* __rest
             nout[ch] = e + (uint32_t)s_overrun;
         }
     if (tid < kMaxCn0) gc->prompt_buffer[tid] = s_pbuf[tid];
+    if constexpr (KF)
+        {
+            KfShared* const ks = kf_shared<true>();
+            const KfSlot& cur = ks->slot[ks->cur];
+            if (tid < 16) gc->kf.P[tid] = cur.P[tid];
+            if (tid < 16) gc->kf.Q[tid] = ks->q[tid];
+            if (tid < 4) gc->kf.x[tid] = cur.x[tid];
+            if (tid < 2) gc->kf.R[tid] = ks->r[tid];
+        }
 }
+
+#ifdef GSDR_TRK_KF_UNIT
+// trk_kf.hip compiles this file a second time for the Kalman kernel instances alone, so
+// that they share no translation unit with the DLL/PLL instances: with both in one unit
+// the flagship DLL/PLL instance (gr_complex, float replicas) came out with one VGPR
+// spilled, where it has none without them.  The kernel types are this
+// unit's copies of the same layouts; the caller launches through its own.
+}  // namespace
+
+namespace gsdr
+{
+const void* trk_kf_kernel(int item_type, bool pack)
+{
+    if (item_type == GSDR_ITEM_GR_COMPLEX)
+        return pack ? (const void*)trk_kernel<GSDR_ITEM_GR_COMPLEX, true, true> : (const void*)trk_kernel<GSDR_ITEM_GR_COMPLEX, false, true>;
+    if (item_type == GSDR_ITEM_CSHORT)
+        return pack ? (const void*)trk_kernel<GSDR_ITEM_CSHORT, true, true> : (const void*)trk_kernel<GSDR_ITEM_CSHORT, false, true>;
+    return pack ? (const void*)trk_kernel<GSDR_ITEM_IBYTE, true, true> : (const void*)trk_kernel<GSDR_ITEM_IBYTE, false, true>;
+}
+}  // namespace gsdr
+#else
 
 // A secondary code / preamble string as the register acquire_secondary compares
 // with: the register holds the signs of the last pushes (1 = real < 0), newest at
@@ -2209,6 +2615,11 @@ void set_secondary(TrkConst& c, const char* str, int len)
 
 }  // namespace
 
+namespace gsdr
+{
+const void* trk_kf_kernel(int item_type, bool pack);  // trk_kf.hip
+}
+
 struct gsdr_trk
 {
     int device{0};
@@ -2231,6 +2642,11 @@ struct gsdr_trk
     bool pack_wanted{false};
     std::vector<char> code_f16, data_f16;
     bool pack{false};
+    // Kalman loop (gsdr_trk_set_kf): the handle launches the KF kernel instance; allowed
+    // until the first gsdr_trk_start
+    bool kf{false};
+    bool started{false};
+    gsdr_trk_kf_conf kf_conf{};
     gsdr_trk_epoch* d_out{nullptr};
     uint32_t* d_nout{nullptr};
     uint32_t out_cap{0};
@@ -2458,6 +2874,7 @@ void init_channel(const gsdr_trk_conf& cf, TrkConst& c, TrkChan& ch)
     c.high_dyn = cf.high_dyn ? 1 : 0;
     // dll_pll_conf.cc:118-123: smoother_length < 1 is set to 1
     c.smoother_length = cf.smoother_length < 1 ? 1 : (int32_t)cf.smoother_length;
+    c.kf_beta = c.code_chip_rate / c.signal_carrier_freq;
     // Exponential_Smoother defaults (exponential_smoother.h:58-63) + dll_pll_veml_tracking.cc:540-552
     sm_set(c.sm[0], cf.cn0_smoother_alpha, 25.0F, 12.0F, cf.cn0_smoother_samples / (int)(c.code_period * 1000.0));
     sm_set(c.sm[1], cf.carrier_lock_test_smoother_alpha, -1.0F, 0.0F, cf.carrier_lock_test_smoother_samples);
@@ -2536,8 +2953,10 @@ size_t lds_for(int code_pad, int data_pad)
 // the kernel instance of an item type and replica layout
 using TrkKernel = void (*)(const TrkConst*, TrkChan*, const float* const*, const float* const*, const void*, uint64_t, uint64_t,
     uint32_t, gsdr_trk_epoch*, uint32_t*, int, int, uint64_t*, int, int, int);
-TrkKernel trk_kernel_of(int item_type, bool pack)
+TrkKernel trk_kernel_of(int item_type, bool pack, bool kf = false)
 {
+    // the Kalman instances (gsdr_trk_set_kf) live in trk_kf.hip's unit
+    if (kf) return reinterpret_cast<TrkKernel>(const_cast<void*>(gsdr::trk_kf_kernel(item_type, pack)));
     if (item_type == GSDR_ITEM_GR_COMPLEX) return pack ? trk_kernel<GSDR_ITEM_GR_COMPLEX, true> : trk_kernel<GSDR_ITEM_GR_COMPLEX>;
     if (item_type == GSDR_ITEM_CSHORT) return pack ? trk_kernel<GSDR_ITEM_CSHORT, true> : trk_kernel<GSDR_ITEM_CSHORT>;
     return pack ? trk_kernel<GSDR_ITEM_IBYTE, true> : trk_kernel<GSDR_ITEM_IBYTE>;
@@ -2578,7 +2997,7 @@ int launch(gsdr_trk* k, const void* iq, uint64_t iq_first, uint64_t iq_items, ui
     const dim3 grid(k->conf.max_channels);
     int chunk = 0, sbuf = 0;
     stream_plan(k->lds_bytes, k->code_pad, k->data_pad, (int)gsdr::item_bytes(k->conf.item_type), chunk, sbuf);
-    const TrkKernel kern = trk_kernel_of(k->conf.item_type, k->pack);
+    const TrkKernel kern = trk_kernel_of(k->conf.item_type, k->pack, k->kf);
     hipLaunchKernelGGL(kern, grid, dim3(kTrkThreads), k->lds_bytes, s, k->d_consts, k->d_chans,
         (const float* const*)k->d_codes, (const float* const*)k->d_data_codes, iq, iq_first, iq_items, max_epochs, out, nout,
         k->code_pad, k->data_pad, timing, k->timing_wall, chunk, sbuf);
@@ -2926,6 +3345,25 @@ int gsdr_trk_start(gsdr_trk* k, int ch, uint32_t prn, const float* code, int cod
     sm_reset(t, 1);
     t.next_sample = nitems_read + (uint64_t)(int64_t)offset;
     *first_sample = t.next_sample;
+    if (k->kf)
+        {
+            // init_kf(0.0, d_carrier_doppler_kf_hz) of the pull-in call (kf_tracking.cc:1824,
+            // :857-895); d_F and d_H follow t.corr_time
+            const gsdr_trk_kf_conf& q = k->kf_conf;
+            TrkKf& f = tc.kf;
+            std::memset(&f, 0, sizeof(f));
+            f.R[0] = std::pow(q.code_disc_sd_chips, 2.0);
+            f.R[1] = std::pow(q.carrier_disc_sd_rads, 2.0);
+            const double qd[4] = {q.code_phase_sd_chips, q.carrier_phase_sd_rad, q.carrier_freq_sd_hz, q.carrier_freq_rate_sd_hz_s};
+            const double pd[4] = {q.init_code_phase_sd_chips, q.init_carrier_phase_sd_rad, q.init_carrier_freq_sd_hz,
+                q.init_carrier_freq_rate_sd_hz_s};
+            for (int i = 0; i < 4; ++i)
+                {
+                    f.Q[5 * i] = std::pow(qd[i], 2.0);
+                    f.P[5 * i] = std::pow(pd[i], 2.0);
+                }
+            f.x[2] = acq_doppler_hz;
+        }
     {
         const int cp = std::max(k->code_pad, (code_samples + 2 * kCodeMargin + 1) & ~1);
         // the compact form only when every channel's two replicas are exact in it;
@@ -2946,6 +3384,62 @@ int gsdr_trk_start(gsdr_trk* k, int ch, uint32_t prn, const float* code, int cod
     GSDR_HIP(hipMemcpyAsync(k->d_consts + ch, &c, sizeof(TrkConst), hipMemcpyHostToDevice, k->stream));
     GSDR_HIP(hipMemcpyAsync(k->d_chans + ch, &tc, sizeof(TrkChan), hipMemcpyHostToDevice, k->stream));
     GSDR_HIP(hipStreamSynchronize(k->stream));
+    k->started = true;
+    return GSDR_OK;
+}
+
+void gsdr_trk_kf_conf_default(gsdr_trk_kf_conf* c)  // Kf_Conf::Kf_Conf (kf_conf.cc)
+{
+    if (!c) return;
+    c->code_disc_sd_chips = 0.2;
+    c->carrier_disc_sd_rads = 0.3;
+    c->code_phase_sd_chips = 0.15;
+    c->carrier_phase_sd_rad = 0.25;
+    c->carrier_freq_sd_hz = 0.6;
+    c->carrier_freq_rate_sd_hz_s = 0.01;
+    c->init_code_phase_sd_chips = 0.5;
+    c->init_carrier_phase_sd_rad = 0.7;
+    c->init_carrier_freq_sd_hz = 5.0;
+    c->init_carrier_freq_rate_sd_hz_s = 1.0;
+}
+
+int gsdr_trk_set_kf(gsdr_trk* k, const gsdr_trk_kf_conf* conf)
+{
+    GSDR_REQUIRE(k && conf, GSDR_E_ARG, "gsdr_trk_set_kf: null argument");
+    const double v[10] = {conf->code_disc_sd_chips, conf->carrier_disc_sd_rads, conf->code_phase_sd_chips,
+        conf->carrier_phase_sd_rad, conf->carrier_freq_sd_hz, conf->carrier_freq_rate_sd_hz_s, conf->init_code_phase_sd_chips,
+        conf->init_carrier_phase_sd_rad, conf->init_carrier_freq_sd_hz, conf->init_carrier_freq_rate_sd_hz_s};
+    for (int i = 0; i < 10; ++i)
+        GSDR_REQUIRE(std::isfinite(v[i]) && v[i] >= 0.0, GSDR_E_ARG, "gsdr_trk_set_kf: value %d (%g) is negative or not finite", i,
+            v[i]);
+    std::lock_guard<std::mutex> lk(k->mu);
+    GSDR_REQUIRE(!k->conf.high_dyn, GSDR_E_UNSUPPORTED, "gsdr_trk_set_kf: the Kalman loop has no high-dynamics branch");
+    GSDR_REQUIRE(!k->started, GSDR_E_STATE, "gsdr_trk_set_kf: a channel has been started");
+    gsdr::DeviceGuard g(k->device);
+    GSDR_HIP(hipFuncSetAttribute((const void*)trk_kernel_of(k->conf.item_type, false, true),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kCuLds - kStaticLdsMargin)));
+    // and the compact-replica instance this handle can launch beside it (gsdr_trk_create)
+    if (k->pack_wanted)
+        GSDR_HIP(hipFuncSetAttribute((const void*)trk_kernel_of(k->conf.item_type, true, true),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kCuLds - kStaticLdsMargin)));
+    k->kf_conf = *conf;
+    k->kf = true;
+    return GSDR_OK;
+}
+
+int gsdr_trk_get_kf_state(gsdr_trk* k, int ch, double x[4], double P[16])
+{
+    GSDR_REQUIRE(k, GSDR_E_ARG, "gsdr_trk_get_kf_state: null handle");
+    GSDR_REQUIRE(ch >= 0 && ch < (int)k->conf.max_channels, GSDR_E_ARG, "gsdr_trk_get_kf_state: channel %d", ch);
+    std::lock_guard<std::mutex> lk(k->mu);
+    GSDR_REQUIRE(k->kf, GSDR_E_STATE, "gsdr_trk_get_kf_state: the handle is not in Kalman mode (gsdr_trk_set_kf)");
+    gsdr::DeviceGuard g(k->device);
+    GSDR_HIP(hipStreamWaitEvent(k->stream, k->last_launch, 0));
+    GSDR_HIP(hipMemcpyAsync(&k->h_chans[ch], k->d_chans + ch, sizeof(TrkChan), hipMemcpyDeviceToHost, k->stream));
+    GSDR_HIP(hipStreamSynchronize(k->stream));
+    const TrkKf& f = k->h_chans[ch].kf;
+    if (x) std::memcpy(x, f.x, sizeof(f.x));
+    if (P) std::memcpy(P, f.P, sizeof(f.P));
     return GSDR_OK;
 }
 
@@ -3238,3 +3732,5 @@ int gsdr_trk_read_profile(gsdr_trk* k, double* kernel_ms, uint32_t* launches)
 }
 
 }  // extern "C"
+
+#endif  // GSDR_TRK_KF_UNIT

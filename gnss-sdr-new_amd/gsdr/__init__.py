@@ -62,6 +62,7 @@ EXPORTED = [
     "gsdr_acq_set_iq_caf", "gsdr_acq_set_iq_codes", "gsdr_acq_run_iq_caf", "gsdr_acq_run_iq_caf_stream",
     "gsdr_acq_dump_iq_caf_rows",
     "gsdr_trk_set_secondary_code",
+    "gsdr_trk_kf_conf_default", "gsdr_trk_set_kf", "gsdr_trk_get_kf_state",
 ]
 
 WIPE_EXACT, WIPE_GENERIC, WIPE_AVX2 = 0, 1, 2
@@ -85,6 +86,13 @@ TRK_CONF_DTYPE = np.dtype([
     ("max_carrier_lock_fail", "i4"), ("enable_fll_pull_in", "i4"), ("enable_fll_steady_state", "i4"),
     ("carrier_aiding", "i4"), ("high_dyn", "i4"), ("track_pilot", "i4"), ("smoother_length", "u4")], align=True)
 assert TRK_CONF_DTYPE.itemsize == 144
+
+# include/gsdr.h gsdr_trk_kf_conf: the Kalman fields of Kf_Conf
+KF_CONF_DTYPE = np.dtype([
+    ("code_disc_sd_chips", "f8"), ("carrier_disc_sd_rads", "f8"), ("code_phase_sd_chips", "f8"),
+    ("carrier_phase_sd_rad", "f8"), ("carrier_freq_sd_hz", "f8"), ("carrier_freq_rate_sd_hz_s", "f8"),
+    ("init_code_phase_sd_chips", "f8"), ("init_carrier_phase_sd_rad", "f8"), ("init_carrier_freq_sd_hz", "f8"),
+    ("init_carrier_freq_rate_sd_hz_s", "f8")], align=True)
 
 TRK_EPOCH_DTYPE = np.dtype([
     ("sample_counter", "u8"), ("state", "i4"), ("consumed", "i4"), ("taps", "f4", (10,)),
@@ -479,6 +487,11 @@ def load():
     L.gsdr_host_unregister.argtypes = [P]
     L.gsdr_trk_set_data_code.argtypes = [P, I, P, I]
     L.gsdr_trk_set_secondary_code.argtypes = [P, I, ctypes.c_char_p, I]
+    if hasattr(L, "gsdr_trk_set_kf"):  # (an earlier build selected by GSDR_LIB for an A/B lacks them)
+        L.gsdr_trk_kf_conf_default.argtypes = [P]
+        L.gsdr_trk_kf_conf_default.restype = None
+        L.gsdr_trk_set_kf.argtypes = [P, P]
+        L.gsdr_trk_get_kf_state.argtypes = [P, I, P, P]
     L.gsdr_trk_run_device.argtypes = [P, P, U64, U64, U32, P, P, P]
     L.gsdr_trk_run.argtypes = [P, P, U64, U64, U32, P, P]
     L.gsdr_trk_get_channel.argtypes = [P, I, P, P, P, P]
@@ -1262,8 +1275,16 @@ def trk_conf_default():
     return c
 
 
+def trk_kf_conf_default():
+    """Kf_Conf's Kalman defaults (gsdr_trk_kf_conf_default) as a one-element structured array."""
+    c = np.zeros(1, KF_CONF_DTYPE)
+    load().gsdr_trk_kf_conf_default(_ptr(c))
+    return c
+
+
 class Tracking:
-    """Device-resident DLL/PLL tracking (dll_pll_veml_tracking) for a pool of channels."""
+    """Device-resident DLL/PLL tracking (dll_pll_veml_tracking) for a pool of channels;
+    after set_kf() the Kalman-filter loop (kf_tracking)."""
 
     def __init__(self, conf, device=0):
         self.conf = np.ascontiguousarray(conf, TRK_CONF_DTYPE).copy()
@@ -1369,6 +1390,19 @@ class Tracking:
         _check(load().gsdr_trk_get_channel(self._h, int(ch), ctypes.byref(st), ctypes.byref(nxt), ctypes.byref(dop),
                                            ctypes.byref(cn0)))
         return {"state": st.value, "next_sample": nxt.value, "carrier_doppler_hz": dop.value, "cn0_db_hz": cn0.value}
+
+    def set_kf(self, conf=None):
+        """Switch the handle to the Kalman loop (gsdr_trk_set_kf) before any start();
+        conf: a one-element KF_CONF_DTYPE array, None for the defaults."""
+        c = trk_kf_conf_default() if conf is None else np.ascontiguousarray(conf, KF_CONF_DTYPE).copy()
+        _check(load().gsdr_trk_set_kf(self._h, _ptr(c)))
+        self.kf_conf = c
+
+    def kf_state(self, ch):
+        """The Kalman filter's (x[4], P[4, 4]) of channel ch after the last launch."""
+        x, P = np.zeros(4, np.float64), np.zeros((4, 4), np.float64)
+        _check(load().gsdr_trk_get_kf_state(self._h, int(ch), _ptr(x), _ptr(P)))
+        return x, P
 
     def save_state(self, slot=0, stream_ptr=0):
         _check(load().gsdr_trk_save_state(self._h, int(slot), ctypes.c_void_p(stream_ptr)))

@@ -62,6 +62,10 @@ public:
     bool high_dyn{false};
     bool dump{false};
     bool dump_mat{true};  // read for parity; the .mat conversion is not reproduced (tracking_dump.h)
+    // set by Kf_Conf (kf_conf.h): the blocks switch their engine handle to the Kalman loop
+    // (gsdr_trk_set_kf) with these values
+    bool kf{false};
+    gsdr_trk_kf_conf kf_conf{};
 };
 
 #endif

@@ -13,6 +13,13 @@ dll_pll_veml_tracking_mi355x::dll_pll_veml_tracking_mi355x(const Dll_Pll_Conf& c
     const gsdr_trk_conf c = d_conf.to_engine(signal, 1);
     if (gsdr_trk_create(device, &c, &d_engine) != GSDR_OK)
         throw std::runtime_error(std::string("dll_pll_veml_tracking_mi355x: ") + gsdr_last_error());
+    if (d_conf.kf && gsdr_trk_set_kf(d_engine, &d_conf.kf_conf) != GSDR_OK)
+        {
+            const std::string why = gsdr_last_error();
+            gsdr_trk_destroy(d_engine);
+            d_engine = nullptr;
+            throw std::runtime_error("dll_pll_veml_tracking_mi355x: " + why);
+        }
     d_vector_length = d_conf.vector_length;
     if (d_conf.dump) d_dump.configure(d_conf.dump_filename);
     d_item_bytes = c.item_type == GSDR_ITEM_CSHORT ? 4 : (c.item_type == GSDR_ITEM_IBYTE ? 2 : 8);

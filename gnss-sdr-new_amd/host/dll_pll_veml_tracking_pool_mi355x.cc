@@ -21,6 +21,13 @@ SharedTrackingPool::SharedTrackingPool(const Dll_Pll_Conf& conf, int32_t signal,
 {
     const gsdr_trk_conf c = d_conf.to_engine(signal, max_channels);
     if (gsdr_trk_create(device, &c, &d_engine) != GSDR_OK) throw gsdr_error("SharedTrackingPool");
+    if (d_conf.kf && gsdr_trk_set_kf(d_engine, &d_conf.kf_conf) != GSDR_OK)
+        {
+            const std::runtime_error err = gsdr_error("SharedTrackingPool");
+            gsdr_trk_destroy(d_engine);
+            d_engine = nullptr;
+            throw err;
+        }
     // the newest window the channels' calls are read from (window_calls vector
     // lengths, twice that of ring positions); the pool advances every channel
     // whenever half a window arrived, so a channel is never more than that behind

@@ -71,6 +71,8 @@ std::unique_ptr<TrackingInterface> GetTrkBlock(const ConfigurationInterface* con
     const int device = device_for_channel(configuration, role, channel);
     if (implementation == "GPS_L1_CA_DLL_PLL_Tracking_MI355X")
         return std::make_unique<GpsL1CaDllPllTrackingMI355X>(configuration, role, in_streams, out_streams, device);
+    if (implementation == "GPS_L1_CA_KF_Tracking_MI355X")
+        return std::make_unique<GpsL1CaKfTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     if (implementation == "Galileo_E1_DLL_PLL_VEML_Tracking_MI355X")
         return std::make_unique<GalileoE1DllPllVemlTrackingMI355X>(configuration, role, in_streams, out_streams, device);
     if (implementation == "Galileo_E5a_DLL_PLL_Tracking_MI355X")

@@ -73,6 +73,39 @@ GpsL1CaDllPllTrackingMI355X::GpsL1CaDllPllTrackingMI355X(const ConfigurationInte
     make_block(configuration, GSDR_SIGNAL_GPS_1C, device);
 }
 
+// gps_l1_ca_kf_tracking.cc:34-93
+GpsL1CaKfTrackingMI355X::GpsL1CaKfTrackingMI355X(const ConfigurationInterface* configuration, const std::string& role,
+    unsigned int in_streams, unsigned int out_streams, int device)
+    : DllPllTrackingAdapterMI355X(role, "GPS_L1_CA_KF_Tracking_MI355X")
+{
+    (void)in_streams;
+    (void)out_streams;
+    Kf_Conf kf_params;
+    kf_params.SetFromConfiguration(configuration, role);
+    trk_params_ = kf_params;  // the Dll_Pll_Conf part carries kf and the Kalman values
+    trk_params_.vector_length = static_cast<uint32_t>(
+        std::round(trk_params_.fs_in / (GPS_L1_CA_CODE_RATE_CPS / GPS_L1_CA_CODE_LENGTH_CHIPS)));
+    if (trk_params_.extend_correlation_symbols < 1)
+        {
+            trk_params_.extend_correlation_symbols = 1;
+            std::cout << "WARNING: GPS L1 C/A. extend_correlation_symbols must be bigger than 1. Coherent integration has "
+                         "been set to 1 symbol (1 ms)\n";
+        }
+    else if (trk_params_.extend_correlation_symbols > 20)
+        {
+            trk_params_.extend_correlation_symbols = 20;
+            std::cout << "WARNING: GPS L1 C/A. extend_correlation_symbols must be lower than 21. Coherent integration has "
+                         "been set to 20 symbols (20 ms)\n";
+        }
+    trk_params_.track_pilot = false;
+    if (trk_params_.high_dyn)
+        throw std::invalid_argument(role + ": the Kalman loop has no high-dynamics branch on this engine (high_dyn=true)");
+    trk_params_.system = 'G';
+    trk_params_.signal[0] = '1';
+    trk_params_.signal[1] = 'C';
+    make_block(configuration, GSDR_SIGNAL_GPS_1C, device);
+}
+
 // galileo_e1_dll_pll_veml_tracking.cc:34-75: extended integration only when
 // tracking the pilot
 GalileoE1DllPllVemlTrackingMI355X::GalileoE1DllPllVemlTrackingMI355X(const ConfigurationInterface* configuration,

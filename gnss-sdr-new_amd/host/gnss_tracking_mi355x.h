@@ -22,6 +22,7 @@
 #include "dll_pll_conf.h"
 #include "dll_pll_veml_tracking_mi355x.h"
 #include "dll_pll_veml_tracking_pool_mi355x.h"
+#include "kf_conf.h"
 #include "tracking_block_mi355x.h"
 #include "tracking_interface.h"
 
@@ -65,6 +66,17 @@ class GpsL1CaDllPllTrackingMI355X : public DllPllTrackingAdapterMI355X
 public:
     GpsL1CaDllPllTrackingMI355X(const ConfigurationInterface* configuration, const std::string& role,
         unsigned int in_streams, unsigned int out_streams, int device = 0);
+};
+
+// GpsL1CaKfTracking (src/algorithms/tracking/adapters/gps_l1_ca_kf_tracking.cc), Tracking_1C.implementation =
+// GPS_L1_CA_KF_Tracking_MI355X: Kf_Conf from the role (kf_conf.h), the same vector_length, clamp of
+// extend_correlation_symbols to 1-20 and track_pilot = false as the DLL/PLL adapter, and the same blocks
+// with their engine handle in the Kalman loop
+class GpsL1CaKfTrackingMI355X : public DllPllTrackingAdapterMI355X
+{
+public:
+    GpsL1CaKfTrackingMI355X(const ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams,
+        unsigned int out_streams, int device = 0);
 };
 
 class GalileoE1DllPllVemlTrackingMI355X : public DllPllTrackingAdapterMI355X

@@ -1030,6 +1030,46 @@ int gsdr_trk_get_channel(gsdr_trk* trk, int ch, int32_t* state, uint64_t* next_s
 int gsdr_trk_save_state(gsdr_trk* trk, int slot, void* stream);
 int gsdr_trk_restore_state(gsdr_trk* trk, int slot, void* stream);
 
+/* Kalman-filter tracking loop (kf_tracking.cc of the reference): the discriminator ->
+ * loop filter -> NCO chain of a handle is replaced by a four-state Kalman filter
+ * (code-phase error [chips], carrier phase [rad], Doppler [Hz], Doppler rate [Hz/s])
+ * driven by both discriminators; state machine, correlators, lock detectors and bit
+ * synchronisation stay as they are.  The fields are the Kalman fields of Kf_Conf
+ * (standard deviations; the filter uses their squares). */
+typedef struct gsdr_trk_kf_conf
+{
+    double code_disc_sd_chips;   /* measurement noise R (pull-in; narrow tracking re-derives R from C/N0) */
+    double carrier_disc_sd_rads;
+    double code_phase_sd_chips;  /* process noise Q */
+    double carrier_phase_sd_rad;
+    double carrier_freq_sd_hz;
+    double carrier_freq_rate_sd_hz_s;
+    double init_code_phase_sd_chips;  /* initial covariance P0 */
+    double init_carrier_phase_sd_rad;
+    double init_carrier_freq_sd_hz;
+    double init_carrier_freq_rate_sd_hz_s;
+} gsdr_trk_kf_conf;
+
+/* The Kf_Conf constructor's values: 0.2, 0.3, 0.15, 0.25, 0.6, 0.01, 0.5, 0.7, 5, 1. */
+void gsdr_trk_kf_conf_default(gsdr_trk_kf_conf* conf);
+
+/* Switches the handle to the Kalman loop, for every channel and for good.  Only while
+ * no channel has been started (GSDR_E_STATE otherwise); a negative or non-finite value
+ * is GSDR_E_ARG; a handle created with high_dyn is GSDR_E_UNSUPPORTED (kf_tracking's
+ * high-dynamics branch is not implemented).  A refused call leaves the handle as it
+ * was.  In Kalman mode fll_bw_hz, pll_bw*, dll_bw*, the filter orders, enable_fll_* and
+ * carrier_aiding are ignored: the code frequency is always chip_rate + doppler *
+ * chip_rate / carrier.  The four log fields of gsdr_trk_epoch carry what
+ * kf_tracking::log_data dumps in their place (carrier discriminator [Hz], (float)x(2),
+ * code discriminator, (float) code error estimate); evm, carrier_rate and code_rate
+ * are 0. */
+int gsdr_trk_set_kf(gsdr_trk* trk, const gsdr_trk_kf_conf* conf);
+
+/* The filter's state x (4) and covariance P (16, row-major) of channel ch; synchronous,
+ * ordered after the handle's last launch like gsdr_trk_get_channel.  GSDR_E_STATE on a
+ * handle that is not in Kalman mode. */
+int gsdr_trk_get_kf_state(gsdr_trk* trk, int ch, double x[4], double P[16]);
+
 /* Kernel-time profiling with HIP events (see gsdr_acq_set_profiling). */
 int gsdr_trk_set_profiling(gsdr_trk* trk, int enable);
 
