@@ -137,7 +137,7 @@ def test_streamed_chunk_tails(fs):
     the last chunk (16896), one sample more -- a chunk of its own (16897) --, the same
     at a half-sample code period (16896.5: calls consume 16896 and 16897 samples in
     turn), a tail of several blocks (20000) and a short one behind three chunks (24600).  The
-    chunk / tail split (csrc/trk.hip correlate_call_stream) must not change a sum."""
+    chunk / tail split (csrc/trk_correlate.h correlate_call_stream) must not change a sum."""
     sats = synth.random_constellation(2, seed_offset=37, cn0_dbhz=45.0)
     for s in sats:
         s.code_doppler = True
